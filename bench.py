@@ -2,6 +2,12 @@
 """HYBRID9 hot-path benchmark on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times its K steps and prints the result
+line.  ``--dump-outputs DIR`` then writes what the last timed step left a
+caller (annual means, state, diagnostics) as DIR/<name>.npy; ``--full``
+adds the secondary measurements, ``isolated`` and ``cpu_baseline`` below.
 
 A *step* is one simulated calendar year for every land cell of the GPU:
 365/366 days x NISURF substeps of HYDROLOGY (+ daily GROW when enabled).
@@ -10,10 +16,11 @@ order -- decade -> cell -> year, smp carried from cell to cell
 (HYBRID9.f90:93-130), bit-identical to the reference -- as one
 ``h9g_run_ordered`` call over whole reference decades: the untimed warm-up
 is rounded up to whole decades (``--warmup 5`` runs 1901-1910) and the
-timed years must be whole decades (``--steps 20``: 1911-1930).
+timed years are whole decades (``--steps 20``: 1911-1930) and, where K is
+no multiple of 10, a shorter last one (``--steps 13``: 1911-1923).
 ``--order isolated`` times ``h9g_run_year`` launches (every cell its own
 smp, the contract of rounds 1-5; it misses the reference by up to 4e-2,
-DESIGN.md §2); the default run reports it under ``isolated``.  The FP64
+DESIGN.md §2); a ``--full`` run reports it under ``isolated``.  The FP64
 diagnostics are all-reduced across GPUs over RCCL (torch.distributed
 "nccl") after each call (cell order) or year (isolated).
 Inputs (soil parameters, a distinct forcing year per step) are generated on
@@ -31,7 +38,7 @@ riding re-runs, and its year-1 re-runs) / the launch's device time from HIP
 events on the kernel's stream.
 ``cpu_baseline`` times the reference itself (oracle/_ref/h9ref: unmodified
 HYDROLOGY.f90 compiled with amdflang) on a bounded sample of the same
-workload, one process per host core, rank 0 at N=1 only.
+workload, one process per host core, rank 0 at N=1 with ``--full`` only.
 """
 from __future__ import annotations
 
@@ -99,14 +106,13 @@ def dist_setup(n_gpus: int):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != n_gpus:
         raise SystemExit(f"--gpus {n_gpus} but WORLD_SIZE={world}; launch N>1 with torchrun")
+    # torch is plumbing for the ranks' exchange only: one rank alone does not
+    # load it (seconds of start-up; ctx.sync() waits for both of the context's
+    # streams, and nothing else is queued on the device)
     torch = dist = None
-    try:
+    if world > 1:
         import torch  # noqa: F811
         import torch.distributed as dist  # noqa: F811
-    except Exception:                        # torch is plumbing only
-        if world > 1:
-            raise
-    if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
         dist.init_process_group("nccl")      # RCCL over xGMI on ROCm
@@ -432,26 +438,31 @@ def diag_exchange(ctx, torch, dist, device: str):
 
 
 def ordered_years(ctx, pl: dict, s0: int, s1: int, exchange, work: list) -> None:
-    """Steps s0 .. s1-1, whole reference decades (HYBRID9.f90:93-130), as
-    one h9g_run_ordered call: the decades overlap on the device and every
-    year's forcing stays resident."""
-    if s1 <= s0:
-        return
-    ctx.run_ordered([pl["slot_of_step"][k] for k in range(s0, s1)], pl["years"][s0], raise_on_stop=False,
-                    annual=False)
-    work.append(dict(ctx.decade_stats(), overlap=ctx.ordered_stats(), years=s1 - s0))
-    if exchange:
-        exchange()
+    """Steps s0 .. s1-1, reference decades from a decade's first year
+    (HYBRID9.f90:93-130), as one h9g_run_ordered call: the decades overlap
+    on the device and every year's forcing stays resident.  A call's years
+    need distinct slots, so more years than the ring holds in whole decades
+    go as several calls, each of whole decades but the last."""
+    a = s0
+    while a < s1:
+        b = s1 if s1 - a <= pl["nslots"] else a + (pl["nslots"] // 10 * 10 or pl["nslots"])
+        ctx.run_ordered([pl["slot_of_step"][k] for k in range(a, b)], pl["years"][a], raise_on_stop=False,
+                        annual=False)
+        work.append(dict(ctx.decade_stats(), overlap=ctx.ordered_stats(), years=b - a))
+        if exchange:
+            exchange()
+        a = b
 
 
 def decade_aligned(W: int, K: int) -> tuple[int, int]:
     """The cell order's warm-up and timed years: the warm-up rounded up to
-    whole decades from 1901; the timed years must be whole decades, since a
-    cut decade is not the reference's order (a cell's successor would start
-    from its smp in the middle of the decade)."""
-    if K < 10 or K % 10:
-        raise SystemExit(f"--order cell times whole reference decades: --steps {K} is not a multiple of 10 "
-                         "(use --order isolated for other counts)")
+    whole decades from 1901, so the K timed years start with a decade of the
+    reference.  They run as whole decades and, where K is no multiple of 10,
+    a shorter last one, as the reference's own last decade is (HYBRID9.f90:
+    109-113); a decade is never cut at its start (a cell's successor would
+    start from its smp in the middle of the decade)."""
+    if K < 1:
+        raise SystemExit(f"--order cell: --steps {K} times no year")
     return (W + 9) // 10 * 10, K
 
 
@@ -513,16 +524,69 @@ def timed_steps(ctx, pl: dict, exchange, sync, order: str = "isolated", work: li
     return time.perf_counter() - t0
 
 
+DUMP_BUDGET = 64e6              # bytes --dump-outputs may write in all
+
+
+def dump_outputs(ctx, diag, directory, rank: int = 0, failed: int | None = None) -> dict:
+    """--dump-outputs: what a caller holds after the last timed step, as
+    DIR/<name>.npy (rank r > 0: <name>_rank<r>.npy):
+      annual       f32 (12+L, cells)  annual means of the last year (h9g_get_annual)
+      state        f32 (cells, 4L+9)  every cell's state after it, the fields of
+                                      h9g_get_state side by side
+      cells        f64 (cells,)       the context index of each cell written
+      diagnostics  f64 (NDIAG,)       the last year's FP64 diagnostics
+    Where the arrays exceed DUMP_BUDGET, they keep the same fixed, seeded
+    sample of the cells (ascending context order).  A cell that reached one
+    of the reference's STOPs computes no further and its annual means are
+    NaN (h9g.h): such cells are left out, as `value` leaves them out, so
+    every number written is finite; `failed` (this context's failed_cells)
+    must account for every cell left out of an unsampled dump.  Returns the
+    `outputs` entry of the result line."""
+    L, n = ctx.L, ctx.ncell
+    annual, packed = ctx.get_annual(), ctx.get_state()
+    widths = [L, L, L, L + 1] + [1] * 8          # h9g.h: the packed state's fields, each (cells, width)
+    offs = np.concatenate([[0], np.cumsum([w * n for w in widths])])
+    state = np.concatenate([packed[offs[k]:offs[k + 1]].reshape(n, w) for k, w in enumerate(widths)], axis=1)
+    keep = int(DUMP_BUDGET - 4096) // (4 * (annual.shape[0] + state.shape[1]) + 8)
+    cells = np.arange(n)
+    if keep < n:
+        cells = np.sort(np.random.default_rng(20240607).choice(n, size=keep, replace=False))
+    stopped = np.isnan(annual[:, cells]).any(axis=0)
+    if failed is not None and keep >= n and int(stopped.sum()) != failed:
+        raise RuntimeError(f"--dump-outputs: {int(stopped.sum())} cells have NaN annual means, {failed} cells STOPped")
+    cells = cells[~stopped]
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    arrays = {"annual": np.ascontiguousarray(annual[:, cells], np.float32),
+              "state": np.ascontiguousarray(state[cells], np.float32),
+              "cells": cells.astype(np.float64), "diagnostics": np.asarray(diag, np.float64)}
+    for name, a in arrays.items():
+        np.save(d / f"{name}{sfx}.npy", a)
+    return {"dir": str(d), "cells": int(cells.size), "of_cells": int(n), "stopped_left_out": int(stopped.sum()),
+            "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
-                    help="timed years (cell order: whole decades, default 20; isolated: default 3; config4: 30)")
+                    help="timed years (cell order: default 20, whole decades and a shorter last one where it is no "
+                         "multiple of 10; isolated: default 3; config4: 30)")
     ap.add_argument("--warmup", type=int, default=None,
                     help="untimed years (cell order: rounded up to whole decades, default 10; isolated: default "
                          "1; config4: 0)")
     ap.add_argument("--workload", default="config2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements: the reference on the host "
+                         "cores (`cpu_baseline`) and the isolated-cell contract (`isolated`); a plain run only "
+                         "sets up, warms up, times its steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them left a caller as DIR/<name>.npy: "
+                         "annual (f32), state (f32), cells (f64), diagnostics (f64), all finite (cells that reached "
+                         "a STOP of the reference are left out); the same arguments give the same inputs, so two "
+                         "builds can be compared array for array")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: shard one fixed grid over the ranks (default: weak, "
@@ -535,9 +599,9 @@ def main():
                          "smp carried from cell to cell, bit-identical to the reference); isolated: every cell "
                          "its own smp (h9g_run_year per year; the default with --host-fed / --forcing nc4)")
     ap.add_argument("--no-isolated-line", action="store_true",
-                    help="skip the secondary measurement of the isolated-cell contract (the default cell-order "
-                         "run at N=1 adds it: 1901-1905 untimed, 1906-1925 timed, reported under `isolated`, "
-                         "never as `value`)")
+                    help="with --full: skip the secondary measurement of the isolated-cell contract (a --full "
+                         "cell-order run of 25 years or more at N=1 adds it: 1901-1905 untimed, 1906-1925 timed, "
+                         "reported under `isolated`, never as `value`)")
     ap.add_argument("--forcing", choices=["device", "nc4"], default="device",
                     help="nc4: every step's forcing is read from synthetic PGF netCDF-4 files through "
                          "h9g_nc_forcing_prefetch (ingest-inclusive, isolated order; DESIGN.md, never as `value`)")
@@ -645,6 +709,9 @@ def main():
     # cells that hit a reference STOP stop computing: count only the others
     # (diag is the all-reduced sum over ranks for N > 1)
     failed = int(round(float(diag[11])))
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(ctx, diag, args.dump_outputs, rank, failed if world == 1 else None)
     steps_per_cell = sum(synth.days_in_year(y) * ns for y in years[W:])
     cell_steps_rank = (n_total - failed) / world * steps_per_cell
     value = (n_total - failed) * steps_per_cell / elapsed
@@ -710,8 +777,10 @@ def main():
                              "rerun_cell_years_per_cell_year": sum(w["rerun_cell_years"] for w in work) /
                              max(1.0, float(gid.size * K)),
                              "warmup_years_run": W}
-        if (world == 1 and not args.no_isolated_line and len(pl["years"]) >= 25):
+        if (args.full and world == 1 and not args.no_isolated_line and len(pl["years"]) >= 25):
             out["isolated"] = isolated_line(ctx, pl, ns, sync)
+    if dumped is not None:
+        out["outputs"] = dumped
     if host_fed is not None:
         out["host_fed"] = host_fed.describe()
         host_fed.close()
@@ -720,7 +789,8 @@ def main():
         out["data"] = "synthetic forcing read from netCDF-4 files each step (tools/pgf_synth.py)"
         subprocess.run(["rm", "-rf", str(Path(nc_fed.paths[0]).parent)])
     ctx.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and host_fed is None and nc_fed is None:
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and host_fed is None
+            and nc_fed is None):
         out["cpu_baseline"] = cpu_baseline(wl, synth.SEED)
     if world > 1:
         dist.barrier()

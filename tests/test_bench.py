@@ -172,8 +172,80 @@ def test_world2_gloo_bench_cell_order():
         assert ncalls == 1                               # the timed call's stats only
         np.testing.assert_array_equal(buf, want)
         assert elapsed >= 0
+    # --steps is the number of timed years: a last decade may be cut short,
+    # the first never (the warm-up still ends with a whole decade)
+    assert bench.decade_aligned(5, 15) == (10, 15) and bench.decade_aligned(11, 3) == (20, 3)
     with pytest.raises(SystemExit):
-        bench.decade_aligned(5, 15)                      # a cut decade is refused
+        bench.decade_aligned(5, 0)                       # no timed year is refused
+
+
+def test_ordered_years_keep_a_calls_slots_distinct():
+    """More timed years than the forcing ring holds: the cell order goes as
+    several h9g_run_ordered calls, each from a decade's first year, of whole
+    decades but the last, with distinct slots; --steps 47 times 47 years."""
+    calls = []
+
+    class Ctx(StubOrderedCtx):
+        def run_ordered(self, slots, year0, **kw):
+            assert len(set(slots)) == len(slots) and (year0 - 1901) % 10 == 0
+            calls.append(len(slots))
+            return super().run_ordered(slots, year0, **kw)
+
+    W, K = bench.decade_aligned(5, 47)
+    pl = bench.plan("config2", W, K)
+    ctx, work = Ctx(0), []
+    bench.timed_steps(ctx, pl, None, lambda: None, "cell", work)
+    assert [y for _, y in ctx.years] == list(range(1901, 1901 + 57))
+    assert calls == [10, 30, 17] and [w["years"] for w in work] == [30, 17]
+
+
+def test_dump_outputs_arrays(tmp_path, monkeypatch):
+    """--dump-outputs writes the last year's annual means, every cell's state
+    (the packed fields side by side), the cells' indices and the diagnostics,
+    every number finite: cells that STOPped (NaN annual means) are left out
+    and must be the context's failed cells; past the byte budget, the same
+    seeded sample of cells in every array, run after run."""
+    L, n = 8, 50
+    ncol = 4 * L + 9
+
+    class Ctx:
+        pass
+    ctx = Ctx()
+    ctx.L, ctx.ncell = L, n
+    want = (np.arange(n)[:, None] * 100 + np.arange(ncol)[None, :]).astype(np.float32)
+    blocks, o = [], 0
+    for w in [L, L, L, L + 1] + [1] * 8:
+        blocks.append(want[:, o:o + w].ravel())
+        o += w
+    annual = np.tile(np.arange(n, dtype=np.float32), (12 + L, 1))
+    annual[:, [7, 31]] = np.nan                       # two cells STOPped
+    live = np.delete(np.arange(n), [7, 31])
+    ctx.get_state = lambda: np.concatenate(blocks)
+    ctx.get_annual = lambda: annual.copy()
+    diag = np.arange(h.NDIAG, dtype=np.float64)
+    info = bench.dump_outputs(ctx, diag, tmp_path / "a", failed=2)
+    assert info["cells"] == n - 2 and info["stopped_left_out"] == 2
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == [
+        "annual.npy", "cells.npy", "diagnostics.npy", "state.npy"]
+    st, an, ce, dg = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("state", "annual", "cells", "diagnostics"))
+    assert st.dtype == np.float32 and an.dtype == np.float32 and ce.dtype == np.float64 and dg.dtype == np.float64
+    assert all(np.isfinite(x).all() for x in (st, an, ce, dg))
+    np.testing.assert_array_equal(ce, live)
+    np.testing.assert_array_equal(st, want[live])
+    np.testing.assert_array_equal(an, annual[:, live])
+    np.testing.assert_array_equal(dg, diag)
+    with pytest.raises(RuntimeError, match="NaN annual means"):
+        bench.dump_outputs(ctx, diag, tmp_path / "x", failed=1)     # a NaN in a cell that did not STOP
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096 + (4 * (12 + L + ncol) + 8) * 20)
+    infos = [bench.dump_outputs(ctx, diag, tmp_path / d, rank=1) for d in ("b", "c")]
+    assert infos[0]["cells"] == 20 - infos[0]["stopped_left_out"] and infos[0]["cells"] == infos[1]["cells"]
+    st, an, ce = (np.load(tmp_path / "b" / f"{k}_rank1.npy") for k in ("state", "annual", "cells"))
+    cells = ce.astype(int)
+    assert cells.size == infos[0]["cells"] and np.all(np.diff(cells) > 0) and not set(cells) & {7, 31}
+    np.testing.assert_array_equal(st, want[cells])
+    np.testing.assert_array_equal(an, annual[:, cells])
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "state_rank1.npy"), st)
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= bench.DUMP_BUDGET
 
 
 def _free_port():

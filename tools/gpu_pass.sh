@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest $TESTS -m gpu -x -v -s --timeout 300 --tim
   > $out/pytest_gpu_$tag.txt 2>&1 || { tail -30 $out/pytest_gpu_$tag.txt; exit 1; }
 tail -3 $out/pytest_gpu_$tag.txt
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke_$tag.txt 2>&1 || { cat $out/smoke_$tag.txt; exit 1; }
-timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $out/bench_${tag}_driver.json 2> $out/bench_${tag}_driver.err || { tail $out/bench_${tag}_driver.err; exit 1; }
+timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $out/bench_${tag}_driver.json 2> $out/bench_${tag}_driver.err || { tail $out/bench_${tag}_driver.err; exit 1; }
 python - "$out/bench_${tag}_driver.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

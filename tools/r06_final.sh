@@ -30,7 +30,7 @@ case "${PART:-1}" in
   echo "== pytest gpu" && timeout -k 10 700 python -u -m pytest tests -x -v -s -m gpu -p no:cacheprovider --timeout 300 \
     --timeout-method thread > gpurun_out/pytest_gpu_$TAG.txt 2>&1
   rc=$?; tail -2 gpurun_out/pytest_gpu_$TAG.txt; [ $rc -eq 0 ] || exit $rc
-  echo "== driver bench" && timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+  echo "== driver bench" && timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full \
     > gpurun_out/bench_${TAG}_driver.json 2> gpurun_out/bench_${TAG}_driver.err
   rc=$?; tail -c 400 gpurun_out/bench_${TAG}_driver.json; echo; [ $rc -eq 0 ] || exit $rc
   OUT=gpurun_out/prof_${TAG}_co
