@@ -313,6 +313,8 @@ h9g_pair11_kernel(const KArgs a, const G g) {
 // short lists of the cell-order re-runs (h9g_run_decade_ordered), whose
 // years run as lone waves: a lone wave's year is latency-bound, and this
 // cuts its per-layer rounds from 3 to 1 at L = 8 (from 5 to 1 at L = 10).
+// Round 7: its powers of the per-layer phases, the single-power round and the
+// aquifer node run as two task rounds, a power per lane (hydrology_pair kTask).
 template <int L, class G>
 __global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(1, 1)))
 h9g_pair1_kernel(const KArgs a, const G g) {

@@ -108,6 +108,10 @@ static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_
 #define H9G_SPARE_L10 0   // spare lanes in the 3-wave L = 10 build too (PairStore::kSpare)
 #endif
 
+#ifndef H9G_P1_TASKS
+#define H9G_P1_TASKS 1   // the one-column wave's powers as two task rounds, a power per lane (hydrology_pair)
+#endif
+
 template <int K>
 struct FV {
   float v[K];
@@ -155,6 +159,31 @@ H9K_HD int lane_geti(int v, int src) {
 #else
   (void)src;
   return v;
+#endif
+}
+
+// value of the wave's lane 0, wave-uniform (v_readlane: no LDS crossbar); the
+// one-column wave's starting state for its task lanes (hydrology_pair)
+H9K_HD float lane0_get(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
+#else
+  return v;
+#endif
+}
+H9K_HD int lane0_geti(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readlane(v, 0);
+#else
+  return v;
+#endif
+}
+// lanes of the wave where p holds (host: bit 0)
+H9K_HD uint64_t lane_mask(bool p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ballot_w64(p);
+#else
+  return p ? 1u : 0u;
 #endif
 }
 
@@ -321,7 +350,11 @@ struct PairStore {
   static constexpr bool kRtsHK = kRts;
   static constexpr int NPF = kRecip ? (kRts ? PF_SVH2O : PF_RTS0) : PF_RPSI0;   // per-layer fields in LDS
   static constexpr int NPS = kDayRecip ? PS_SVZWT : PS_DR0; // per-cell fields in LDS
-  static constexpr int ROWS = NPF * NT + (NPS + 1) / 2;
+  // (a one-column wave, S = 2, keeps the substep's starting theta(1..L) in
+  // NT more rows, float TH0 + i - 1 of the block, for its task lanes:
+  // hydrology_pair)
+  static constexpr int TH0 = (NPF * NT + (NPS + 1) / 2) * S;
+  static constexpr int ROWS = NPF * NT + (NPS + 1) / 2 + (S == 2 ? NT : 0);
   static constexpr int GBLOCK = 65536;                      // bytes per workgroup (>= any LDS address)
   lds_float *self, *even;
   const lds_float *zt;                 // zi(0..L+1), then zi(0..L+1)/1000 (per block)
@@ -752,6 +785,16 @@ H9K_HD void cell_inv_pair(const G &g, const CS &cs) {
   cs.set_sc(PS_TSDZ1, MAXF(zero, (cs.lay(PF_TS, 1) * g.dz(1))));
 }
 
+// The task rounds of hydrology_pair: a wave that holds one column (the store's
+// LANES == 2, Split2 with helper lanes), on the fast path only.
+template <class M, class SP, class CS>
+constexpr bool pair1_tasks() {
+  if constexpr (H9G_P1_TASKS && SP::kSpare && CS::kSpare && !M::kExact)
+    return CS::LANES == 2;
+  else
+    return false;
+}
+
 // One HYDROLOGY call (/root/reference/SOURCE/HYDROLOGY.f90:141-1283) for
 // one cell; every block cites the reference lines it restates.  Returns 0
 // or an H9G_ERR_* code (the reference's STOP sites) with errval set;
@@ -987,6 +1030,12 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // potential, own layers (independent phases)
   float zq[L + 2];
   float hk[L + 1], dhkdw[L + 1], dsmpdw[L + 1];
+  // the single powers and the aquifer node (below); a one-column wave's task
+  // rounds evaluate them with the per-layer phases and leave picks = false
+  constexpr bool kTask = pair1_tasks<M, SP, CS>();
+  FV<1> p0{{zero}}, p1{{zero}};               // lane 0's and lane 1's power
+  FV<2> eA{{zero, zero}}, eS{{zero, zero}};
+  bool picks = true, aq_task = false;
   {
     float *const outq[1] = {zq};
     float *const outk[4] = {hk, dhkdw, smp, dsmpdw};
@@ -1182,7 +1231,196 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           return hk_body([&](int p) __attribute__((always_inline)) { return OWN(p); }, sel(h, theta[i0], theta[i0 + 1]),
                          sel(h, theta[i0 + 1], theta[ip1]), sel(h, TS(i0 + 1), TS(ip1)), bad);
     };
-    if constexpr (SP::kSpare && CS::kSpare && !M::kExact) {
+    if constexpr (kTask) {
+      // One column per wave: a power per lane.  The powers of these phases and
+      // of the single-power and aquifer rounds below have two levels of
+      // dependency, so they take two task rounds.  Every task is
+      //   q = div_d(num, den, stored reciprocal); x = clamp/select(q);
+      //   w = powf_d(x, e); flag = div_bad(q) | powf flag
+      // on the operands of eq_body, hk_body and the two pick rounds:
+      //   round A, lane 4(i-1)+k, layer i, kind k:
+      //     0  b0^expo      (-psi + zw - zi(i-1)) / -psi, 1 where saturated
+      //     1  bi^expo      (-psi + zw - zi(i)) / -psi,   1 where sat or in-layer
+      //     2  s1^(2b+2)    s1 by Markstein from PF_ITS, before the round
+      //     3  s_node^(-b)  theta(i) / ts
+      //   lane 4L   (kind 4) the first single power: aquifer temp0 | recharge ka
+      //   lane 4L+1 (kind 5) the second: specific yield of layer L | jwt+1
+      //   round B, on the lane that holds its operand:
+      //     kind 1  (vol_eq(i) / ts)^(-b), vol_eq from the lane's bi^expo and
+      //             its neighbour's b0^expo (one DPP move)
+      //     kind 4  the aquifer node's zq(L+1), from its temp0
+      //     kind 5  the aquifer node's smp1 (theta(L))
+      // Lanes past 4L+1 repeat the last task; kinds 0, 2 and 3 repeat kind 1's
+      // expressions in round B, unread.  A task's parameters come from the
+      // column's LDS block at the task's layer, theta from the rows the pair
+      // lanes store it to, zwt and jwt from lane 0.  Each lane also evaluates
+      // the rest of its slot's expressions (hk, dhkdw | smp, dsmpdw | zq), so
+      // all of it runs once; the pair lanes then read every layer's results
+      // from the lanes that hold them, and the flags by ballot.  A flagged task
+      // re-runs the pair lanes' slots by eq_exact / hk_exact; a flagged single
+      // or aquifer power re-runs the pick rounds below (picks).  Same
+      // expressions on the same operands: no bit changes.
+      constexpr int NA = 4 * L + 2;
+      (void)outq;
+      static_assert(NA <= 64 && CS::kRecip && CS::kRts && CS::kRtsHK, "a lane per task, every reciprocal stored");
+      const bool st = sp.spare;
+      const int hh = sp.h;
+      int ln = sp.ln;
+      opaque(ln);                          // the task decode recomputed here, not kept as lane masks over the year
+      if (!st) {
+#pragma unroll
+        for (int t = 0; t < NT; t++) cs.wb[CS::TH0 + 2 * t + hh] = sel(hh, theta[2 * t + 1], theta[2 * t + 2]);
+      }
+      const float zw = lane0_get(zwtmm);
+      const int jwu = lane0_geti(jwt);
+      const bool aqu = jwu == L;
+      const int jcu = aqu ? L : jwu + 1;
+      // ---- round A
+      const int ta = ln < NA ? ln : NA - 1;
+      const bool lay_a = ta < 4 * L;
+      const int ka = lay_a ? (ta & 3) : ta - 4 * L + 4;
+      const int ia = lay_a ? (ta >> 2) + 1 : jcu;
+      const int ipa = ia < L ? ia + 1 : L;
+      const lds_float *oa = cs.wb + (ia - 1);
+      const float th = oa[CS::TH0], thp = cs.wb[CS::TH0 + ipa - 1];
+      const float ts_a = oa[PF_TS * L], psi_a = oa[PF_PSI * L], bsw_a = oa[PF_BSW * L];
+      const float ninv_a = oa[PF_NINVB * L], its_a = oa[PF_ITS * L], hks_a = oa[PF_HKS * L];
+      const float pte_a = oa[PF_PTE * L], c3_a = oa[PF_C3 * L];
+      const float tsp_a = cs.wb[PF_TS * L + ipa - 1];
+      const double rpsi_a = join_d(oa[PF_RPSI0 * L], oa[PF_RPSI1 * L]);
+      const double rts_a = join_d(oa[PF_RTS0 * L], oa[PF_RTS1 * L]);
+      const float zlo_a = cs.zi(ia - 1), zhi_a = cs.zi(ia);
+      const bool sat_a = zw <= zlo_a, inl_a = (zw < zhi_a) && (zw > zlo_a);
+      // s1 (hk_body: Markstein's correction from PF_ITS, range-flagged)
+      const float sa = th + thp, sb = ts_a + tsp_a;
+      const float q0 = sa * its_a;
+      float s1 = __builtin_fmaf(__builtin_fmaf(-sb, q0, sa), its_a, q0);
+      const uint32_t ua = __builtin_bit_cast(uint32_t, sa) - 0x21800000u;   // 2^-60
+      const uint32_t ub = __builtin_bit_cast(uint32_t, sb) - 0x21800000u;
+      const bool s1bad = (ua > ub ? ua : ub) >= 0x5d800000u - 0x21800000u;   // 2^60
+      s1 = MINC(one, s1);
+      const bool by_ts = ka == 2 || ka == 3 || (ka == 4 && !aqu);            // theta / ts, else ... / -psi
+      const float nz = (-psi_a + zw) - (ka == 0 ? zlo_a : zhi_a);
+      const float num_a = by_ts ? th : (ka == 5 ? zw : nz);
+      const float q_a = m.div_d(num_a, by_ts ? ts_a : -psi_a, by_ts ? rts_a : rpsi_a);
+      float sn_a = MAXX(q_a, 0.01f);
+      sn_a = MINC(one, sn_a);
+      const bool one_a = (ka == 0 && sat_a) || (ka == 1 && (sat_a || inl_a));
+      const float x_a = ka == 2 ? s1 : (by_ts ? sn_a : (ka == 5 ? one + q_a : (one_a ? one : q_a)));
+      const float e_a = (ka <= 1 || (ka == 4 && aqu)) ? one + ninv_a
+                        : ka == 2                     ? 2.0f * bsw_a + 2.0f
+                        : ka == 3                     ? -bsw_a
+                        : ka == 4                     ? 2.0f * bsw_a + 3.0f
+                                                      : ninv_a;
+      bool sw_a;
+      const float w_a = m.powf_d(x_a, e_a, sw_a);
+      bool f_a = m.div_bad(q_a) | sw_a | (ka == 2 && s1bad);
+      // ---- the rest of hk_body: kind 2 holds hk, dhkdw, kind 3 smp, dsmpdw
+      const float s2 = hks_a * w_a;
+      const float o_hk = x_a * s2;
+      const float o_dhk = (2.0f * bsw_a + 3.0f) * s2 * its_a;
+      float o_sm = psi_a * w_a;
+      o_sm = MAXC(smpmin, o_sm);
+      float o_ds;
+      if constexpr (H9G_HK_MDIV && L <= 8) {
+        bool b3 = false;
+        o_ds = mk_div((-bsw_a) * o_sm, x_a * ts_a, b3);
+        f_a |= ka == 3 && b3;
+      } else {
+        o_ds = (-bsw_a) * o_sm / (x_a * ts_a);
+      }
+      // ---- the rest of eq_body up to vol_eq (:530-558), on kind 1: temp0 is
+      // the even neighbour's power
+      const float t0 = pair_bcast<0>(w_a);
+      const bool inl1 = inl_a && ka == 1;
+      float vin = zero;
+      if (any_lane(inl1)) {
+        H9G_BR(BR_INL);
+        const float d0 = zw - zlo_a;
+#if H9G_INL_MDIV
+        bool bq = false;
+        const float q1 = mk_div(pte_a, d0, bq);
+#else
+        const float q1 = m.div_d(pte_a, d0, recip64(d0));
+        const bool bq = m.div_bad(q1);
+#endif
+        const float voleq1 = q1 * (one - t0);
+        vin = m.div_d(voleq1 * (zw - zlo_a) + ts_a * (zhi_a - zw), zhi_a - zlo_a, cs.rdz_t(ia));
+        f_a |= inl1 && (bq | m.div_bad(vin));
+        vin = MINF(ts_a, vin);
+        vin = MAXF(vin, zero);
+      }
+      float vbl = c3_a * (w_a - t0);
+      vbl = MAXF(vbl, 0.0f);
+      vbl = MINF(ts_a, vbl);
+      const float vol_eq = sat_a ? ts_a : (inl_a ? vin : vbl);
+      // ve of the aquifer node (:579-584), on kind 4 (its layer is L when aq)
+      float ve = zero;
+      if (aqu) {
+        const float d0 = zw - g.zi(L);
+        ve = pte_a / d0 * (1.0f - w_a);
+        ve = MAXF(ve, 0.0f);
+        ve = MINF(ts_a, ve);
+      }
+      const uint64_t fl_a = lane_mask(f_a);
+      pr.mark(2);
+      // ---- round B
+      const float num_b = ka == 4 ? ve : (ka == 5 ? th : vol_eq);
+      const float q_b = m.div_d(num_b, ts_a, rts_a);
+      const float xm_b = MAXX(q_b, 0.01f);
+      float sn_b = MAXX(0.5f * (one + q_b), 0.01f);
+      sn_b = MINC(one, sn_b);
+      const float x_b = ka >= 4 ? (aqu ? (ka == 4 ? xm_b : sn_b) : one) : xm_b;
+      bool sw_b;
+      const float w_b = m.powf_d(x_b, -bsw_a, sw_b);
+      float o_z = psi_a * w_b;
+      o_z = MAXC(smpmin, o_z);
+      float o_dz = zero;
+      if (aqu) o_dz = -bsw_a * o_z / (x_b * ts_a);            // dsmpdw1, on kind 5
+      const uint64_t fl_b = lane_mask((m.div_bad(q_b) | sw_b) && (ka == 1 || (ka >= 4 && aqu)));
+      // ---- every layer's results, from the lanes that hold them (the index
+      // kept in a VGPR: the values stay out of the scalar registers)
+      int vz = 0;
+      opaque(vz);
+#pragma unroll
+      for (int i = 1; i <= L; i++) {
+        const int lb = 4 * (i - 1);
+        zq[i] = lane_get(o_z, vz + lb + 1);
+        hk[i] = lane_get(o_hk, vz + lb + 2);
+        dhkdw[i] = lane_get(o_dhk, vz + lb + 2);
+        smp[i] = lane_get(o_sm, vz + lb + 3);
+        dsmpdw[i] = lane_get(o_ds, vz + lb + 3);
+      }
+      p0.v[0] = lane_get(w_a, vz + 4 * L);
+      p1.v[0] = lane_get(w_a, vz + 4 * L + 1);
+      if (aqu) {
+        eA.v[0] = lane_get(o_z, vz + 4 * L);
+        eS.v[0] = lane_get(o_z, vz + 4 * L + 1);
+        eS.v[1] = lane_get(o_dz, vz + 4 * L + 1);
+      }
+      if (st) return 0;                    // the helper lanes' part ends here
+      // ---- flags (wave-uniform): the pair lanes' exact re-runs
+      constexpr uint64_t ALL_A = (1ull << (4 * L)) - 1;
+      const bool bad_eq = (((fl_a & 0x3333333333333333ull) | (fl_b & 0x2222222222222222ull)) & ALL_A) != 0;
+      const bool bad_hk = (fl_a & 0xCCCCCCCCCCCCCCCCull & ALL_A) != 0;
+      if (__builtin_expect(bad_eq, 0)) {
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          const FV<1> r = eq_exact(t, hh);
+          sp.xchg(r.v[0], zq[2 * t + 1], zq[2 * t + 2]);
+        }
+      }
+      if (__builtin_expect(bad_hk, 0)) {
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          const FV<4> r = hk_exact(t, hh);
+#pragma unroll
+          for (int kk = 0; kk < 4; kk++) sp.xchg(r.v[kk], outk[kk][2 * t + 1], outk[kk][2 * t + 2]);
+        }
+      }
+      aq_task = aqu;
+      picks = ((fl_a >> (4 * L)) & 3) != 0 || (aqu && ((fl_b >> (4 * L)) & 3) != 0);
+    } else if constexpr (SP::kSpare && CS::kSpare && !M::kExact) {
       // Helper lanes (round 4: "spare lanes"; round 5: any number of slots).
       // A wave's C pairs use S = 2C of its 64 lanes; the other H = 64 - S
       // lanes help in these two phases.  The phases take R = ceil(NT S / 64)
@@ -1359,7 +1597,13 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // fall-through below the column evaluates s_y(L) itself for a lane inside.
   // (H9G_AQ_FREE: evaluated by every wave; lanes inside the column take
   // operands that make it an identity and raise no flag)
-  const bool any_aq = H9G_AQ_FREE || any_lane(aq);
+  bool any_aq_v;
+  if constexpr (kTask)
+    any_aq_v = aq_task;                       // one column: uniform
+  else
+    any_aq_v = H9G_AQ_FREE || any_lane(aq);
+  const bool any_aq = any_aq_v;
+  if (!kTask || __builtin_expect(picks, 0)) {   // (a one-column wave: only when a task round flagged one of them)
   const int jc = aq ? L : jwt + 1;            // the layer whose -psi divides
   float s1c = one, bsw_c = zero;              // recharge operands of layer jwt+1 (:866-873)
   if (any_lane(!aq)) {
@@ -1372,7 +1616,6 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     s1c = MINC(one, s_node);
     bsw_c = cs.lay(PF_BSW, jc);
   }
-  FV<1> p0, p1;                               // lane 0's and lane 1's power
   sp.template pick<1>(
       [&](int h) __attribute__((always_inline)) -> FV<1> {
         const float npsi = -cs.lay(PF_PSI, jc);
@@ -1390,8 +1633,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
         return FV<1>{{w}};
       },
       p0, p1);
-  const FV<1> pA = p0, pY = p1;
-  FV<2> eA{{zero, zero}}, eS{{zero, zero}};
+  const FV<1> pA = p0;
   if (any_aq) {
   H9G_BR(BR_ANYAQ);
   {
@@ -1428,6 +1670,8 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
         eA, eS);
   }
   }  // any_aq
+  }  // picks
+  const FV<1> pY = p1;
   zq[L + 1] = aq ? eA.v[0] : zero;
   const float smp1 = eS.v[0], dsmpdw1 = eS.v[1];
   cs.launder();

@@ -55,6 +55,18 @@ def kernels(co: Path) -> list[dict]:
     return [k for k in out if "name" in k]
 
 
+def code_sizes(co: Path) -> dict[str, int]:
+    """Bytes of machine code per kernel: the size of its FUNC symbol."""
+    syms = subprocess.run([str(LLVM / "llvm-readelf"), "-s", "-W", str(co)], capture_output=True, text=True,
+                          check=True).stdout
+    out = {}
+    for line in syms.splitlines():
+        f = line.split()
+        if len(f) >= 8 and f[3] == "FUNC":
+            out[f[7]] = int(f[2], 0)
+    return out
+
+
 def demangle(names: list[str]) -> list[str]:
     r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True)
     return r.stdout.splitlines() if r.returncode == 0 else names
@@ -64,18 +76,19 @@ def main() -> None:
     pos = [a for a in sys.argv[1:] if not a.startswith("--")]
     lib = Path(pos[0]) if pos else ROOT / "hybrid9_amd" / "lib" / "libh9g.so"
     with tempfile.TemporaryDirectory() as t:
-        ks = kernels(code_object(lib, Path(t)))
+        co = code_object(lib, Path(t))
+        ks, sizes = kernels(co), code_sizes(co)
     names = demangle([k["name"] for k in ks])
     print(f"{lib.name}: {len(ks)} kernels")
     print(f"{'kernel':60s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'VGPR spill':>10s} {'SGPR spill':>10s} "
-          f"{'private B':>9s} {'LDS B':>7s}")
+          f"{'private B':>9s} {'LDS B':>7s} {'code B':>7s}")
     for k, nm in sorted(zip(ks, names), key=lambda x: x[1]):
         if "--all" not in sys.argv and not re.search(r"h9g_(pair|pair1|pair2|pair11|solo)_kernel", nm):
             continue
         short = nm.replace("h9k::", "").replace("(KArgs, ", "(")
         print(f"{short[:60]:60s} {k.get('vgpr', 0):5d} {k.get('agpr', 0):5d} {k.get('sgpr', 0):5d} "
               f"{k.get('vgpr_spill', 0):10d} {k.get('sgpr_spill', 0):10d} {k.get('private_bytes', 0):9d} "
-              f"{k.get('lds_bytes', 0):7d}")
+              f"{k.get('lds_bytes', 0):7d} {sizes.get(k['name'], 0):7d}")
 
 
 if __name__ == "__main__":
