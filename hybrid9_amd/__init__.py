@@ -26,6 +26,7 @@ if os.environ.get("H9G_LIB"):          # alternative build (e.g. the H9G_STAMPS 
 NFORCING = 7
 NANNUAL_SCALARS = 11
 NDIAG = 12
+NDAILY = 11              # H9G_NDAILY: the daily diagnostics line (site.DIAG_FIELDS)
 ANNUAL_SCALARS = ("npp", "plant_mass", "rnf", "evap", "tas", "rlds", "rsds",
                   "huss", "ps", "pr", "rhs")
 DIAG_NAMES = ("cells", "rnf_sum", "theta_total_sum", "zwt_sum", "wa_sum",
@@ -142,6 +143,8 @@ def lib() -> C.CDLL:
         "h9g_last_soil_slow": (C.c_int, [vp]),
         "h9g_get_params": (C.c_int, [vp, _FP, _FP, _FP, _FP, _FP]),
         "h9g_run_site": (C.c_int, [vp, C.c_int, _FP, _FP, _FP, _FP]),
+        "h9g_set_daily": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32)]),
+        "h9g_get_daily": (C.c_int, [vp, C.c_int, _FP]),
         "h9g_host_expf": (C.c_float, [C.c_float]),
         "h9g_host_powf": (C.c_float, [C.c_float, C.c_float]),
     }
@@ -346,6 +349,7 @@ class Context:
     # -- hot path ---------------------------------------------------------
     def run_year(self, slot: int, jyear: int):
         _check(self._lib.h9g_run_year(self._h, slot, jyear), "h9g_run_year")
+        self.daily_years = [jyear]
 
     def run_decade_ordered(self, slots, jyear0: int, raise_on_stop: bool = True, annual: bool = True):
         """One decade of the reference's own cell order (h9g_run_decade_ordered:
@@ -355,6 +359,7 @@ class Context:
         sl = np.ascontiguousarray(slots, dtype=np.int32)
         out = np.empty((sl.size, 12 + self.L, self.ncell), dtype=np.float32) if annual else None
         np_ = C.c_int32(0)
+        self.daily_years = [jyear0 + k for k in range(sl.size)]
         rc = _check(self._lib.h9g_run_decade_ordered(self._h, sl.ctypes.data_as(C.POINTER(C.c_int32)), jyear0,
                                                      sl.size, _fp(out) if annual else None, C.byref(np_)),
                     "h9g_run_decade_ordered")
@@ -373,6 +378,7 @@ class Context:
         sl = np.ascontiguousarray(slots, dtype=np.int32)
         out = np.empty((sl.size, 12 + self.L, self.ncell), dtype=np.float32) if annual else None
         np_ = (C.c_int32 * max(1, len(decades(jyear0, sl.size))))()
+        self.daily_years = [jyear0 + k for k in range(sl.size)]
         rc = _check(self._lib.h9g_run_ordered(self._h, sl.ctypes.data_as(C.POINTER(C.c_int32)), jyear0, sl.size,
                                               _fp(out) if annual else None, np_), "h9g_run_ordered")
         self.decade_rc = rc
@@ -440,6 +446,35 @@ class Context:
             raise ReferenceStop(self.last_error())
         self.site_rc = rc
         return out
+
+    # -- daily diagnostics of selected cells ------------------------------
+    def set_daily(self, cells=()):
+        """Selects the cells (context indices, strictly increasing) whose
+        daily line (HYBRID9.f90:221-229, site.DIAG_FIELDS) the next run_year,
+        run_decade_ordered or run_ordered records (h9g_set_daily); an empty
+        list turns it off.  The year kernels are untouched: the selected
+        cells are run once more by a small shadow kernel."""
+        c = np.ascontiguousarray(cells if cells is not None else (), dtype=np.int32).ravel()
+        rc = self._lib.h9g_set_daily(self._h, int(c.size), c.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc == -1:
+            raise ValueError("set_daily: cells must be strictly increasing context indices in [0, ncell)")
+        _check(rc, "h9g_set_daily")
+        self._nsel = int(c.size)
+        self._daily_days = []
+
+    def get_daily(self, k: int = 0) -> np.ndarray:
+        """The daily lines of year k (0-based) of the last run_year (k = 0)
+        or ordered call: (ndays, 11, nsel), selection order (h9g_get_daily).
+        The year is the k-th of that call (``daily_years`` names them)."""
+        years = getattr(self, "daily_years", [])
+        nsel = getattr(self, "_nsel", 0)
+        nt = days_in_year(years[k]) if 0 <= k < len(years) else 366
+        out = np.empty((nt, NDAILY, max(nsel, 1)), dtype=np.float32)
+        rc = self._lib.h9g_get_daily(self._h, int(k), _fp(out))
+        if rc == -4:
+            raise H9GError("h9g_get_daily: nothing recorded (H9G_ESTATE): select cells with set_daily, then run")
+        _check(rc, "h9g_get_daily")
+        return out[:, :, :nsel]
 
     def sync(self, raise_on_stop: bool = True) -> int:
         rc = _check(self._lib.h9g_sync(self._h), "h9g_sync")
@@ -566,7 +601,7 @@ def decades(year0: int, nyears: int):
 
 
 def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
-                   state0: np.ndarray | None = None, device=0, chains=None, pipelined=True):
+                   state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None):
     """``run`` in the reference's own cell order (smp carried from cell to
     cell, cells in the given order; chains: a reference rank per cell, each
     rank its own chain, shard.reference_blocks).  pipelined: one
@@ -574,13 +609,17 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
     resident, the decades overlapping on the device); else decade by decade
     through ``Context.run_decade_ordered``.  Returns dict(annual, state, rc,
     err, errors, passes (per decade), work (decade_stats per call),
-    overlap (ordered_stats, pipelined))."""
+    overlap (ordered_stats, pipelined)).  daily_cells: the cells whose daily
+    line is recorded (Context.set_daily) -> out["daily"] (ndays, 11, nsel); the
+    decades then run one after another."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device,
                  nslots=nyears if pipelined else 10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
+        if daily_cells is not None:
+            ctx.set_daily(daily_cells)
         if state0 is None:
             ctx.init_state()
         else:
@@ -595,23 +634,29 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             a, passes = ctx.run_ordered(list(range(nyears)), year0, raise_on_stop=False)
             rc = ctx.decade_rc
             if not rc or len(decades(year0, nyears)) == 1:
-                return dict(annual=a, state=ctx.get_state(), rc=rc, err=ctx.last_error() if rc else None,
-                            errors=ctx.get_errors(), passes=passes, work=[ctx.decade_stats()],
-                            overlap=ctx.ordered_stats())
+                out = dict(annual=a, state=ctx.get_state(), rc=rc, err=ctx.last_error() if rc else None,
+                           errors=ctx.get_errors(), passes=passes, work=[ctx.decade_stats()],
+                           overlap=ctx.ordered_stats())
+                if daily_cells is not None:
+                    out["daily"] = np.concatenate([ctx.get_daily(k) for k in range(nyears)])
+                return out
     if pipelined:
         # a STOP: the reference program ends in that decade, while run_ordered
         # goes on with the other cells; the decade-by-decade form stops there
         return run_cell_order(zi=zi, params=params, forcing=forcing, nisurf=nisurf, year0=year0, nyears=nyears,
-                              grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False)
+                              grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False,
+                              daily_cells=daily_cells)
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device, nslots=10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
+        if daily_cells is not None:
+            ctx.set_daily(daily_cells)
         if state0 is None:
             ctx.init_state()
         else:
             ctx.set_state(state0)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
-        d0, rc, err, passes, work = 0, 0, None, [], []
+        d0, rc, err, passes, work, daily = 0, 0, None, [], [], []
         for y0, ny in decades(year0, nyears):
             for k in range(ny):
                 nt = days_in_year(y0 + k)
@@ -621,16 +666,21 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             ann[y0 - year0:y0 - year0 + ny] = a
             passes.append(p)
             work.append(ctx.decade_stats())
+            if daily_cells is not None:
+                daily += [ctx.get_daily(k) for k in range(ny)]
             rc = ctx.decade_rc
             if rc:
                 err = ctx.last_error()
                 break
-        return dict(annual=ann, state=ctx.get_state(), rc=rc, err=err, errors=ctx.get_errors(), passes=passes,
-                    work=work)
+        out = dict(annual=ann, state=ctx.get_state(), rc=rc, err=err, errors=ctx.get_errors(), passes=passes,
+                   work=work)
+        if daily_cells is not None:
+            out["daily"] = np.concatenate(daily)
+        return out
 
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
-        state0: np.ndarray | None = None, device=0, stop_on_error=True):
+        state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -638,7 +688,9 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     ncell), state (packed), rc, err, errors).  A cell reaching one of the
     reference's STOPs stops (NaN means); with stop_on_error the run ends
     after that year, as the reference program would, else the other cells
-    go on.  ``errors`` holds every cell's STOP record (Context.get_errors)."""
+    go on.  ``errors`` holds every cell's STOP record (Context.get_errors).
+    daily_cells: the cells whose daily line is recorded (Context.set_daily)
+    -> out["daily"] (ndays of the years run, 11, nsel)."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device) as ctx:
@@ -647,17 +699,24 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             ctx.init_state()
         else:
             ctx.set_state(state0)
+        if daily_cells is not None:
+            ctx.set_daily(daily_cells)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
-        d0, rc, err = 0, 0, None
+        d0, rc, err, daily = 0, 0, None, []
         for y in range(nyears):
             nt = days_in_year(year0 + y)
             ctx.push_forcing(y % 2, forcing[:, d0:d0 + nt, :])
             ctx.run_year(y % 2, year0 + y)
             rc = ctx.sync(raise_on_stop=False)
             ann[y] = ctx.get_annual()
+            if daily_cells is not None:
+                daily.append(ctx.get_daily())
             d0 += nt
             if rc:
                 err = ctx.last_error()
                 if stop_on_error:
                     break
-        return dict(annual=ann, state=ctx.get_state(), rc=rc, err=err, errors=ctx.get_errors())
+        out = dict(annual=ann, state=ctx.get_state(), rc=rc, err=err, errors=ctx.get_errors())
+        if daily_cells is not None:
+            out["daily"] = np.concatenate(daily)
+        return out

@@ -792,6 +792,92 @@ __global__ void __launch_bounds__(64) h9g_site_kernel(const SiteArgs a, const G 
   }
 }
 
+// Daily diagnostics of the selected cells (h9g_set_daily): the shadow run
+// cell_focus of h9g_pair.h, one lane per selected cell.  It reads the cells'
+// start state from a gathered copy (st: state rows of nsel, selection order;
+// h9g_focus_gather_kernel), their parameters and forcing by cell id from the
+// context's arrays and the forcing slots' original layout, and writes only
+// out (days of all years, 11, nsel).
+struct FocusArgs {
+  int ncell, nsel, nyears, nisurf, grow_on;
+  size_t fvar;
+  const float *__restrict__ par;
+  const float *__restrict__ st;
+  const int *__restrict__ sel;
+  const int *__restrict__ err;     // the cells' STOP records when the run starts (rows of ncell)
+  const FocusYear *__restrict__ yrs;
+  float *__restrict__ out;
+};
+
+// dst[r][j] = st[r][sel[j]] for every state row; the smp rows from `guess`
+// (L rows of n) instead where given (the cell order: the smp a cell's first
+// substep of the decade reads is its predecessor's, h9g_chain_kernel).
+__global__ void __launch_bounds__(256) h9g_focus_gather_kernel(int nsel, int n, int srows, int L,
+                                                               const int *__restrict__ sel,
+                                                               const float *__restrict__ st,
+                                                               const float *__restrict__ guess,
+                                                               float *__restrict__ dst) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nsel) return;
+  const int c = sel[j];
+  for (int r = 0; r < srows; r++) dst[(size_t)r * nsel + j] = st[(size_t)r * n + c];
+  if (guess)
+    for (int i = 0; i < L; i++) dst[(size_t)(2 * L + i) * nsel + j] = guess[(size_t)i * n + c];
+}
+
+template <int L, class G>
+__global__ void __launch_bounds__(64) h9g_focus_kernel(const FocusArgs a, const G g) {
+  typedef SoloStore<L> SS;
+  __shared__ uint64_t s_e2[32];
+  __shared__ double s_l2[32];
+  __shared__ float s_cell[SS::ROWS * 64];
+  __shared__ float s_zt[zt_size<L>()];
+  if (threadIdx.x == 0) fill_zt<L>(g, s_zt);
+  load_tabs(s_e2, s_l2);
+  const h9m::Tabs T = {s_e2, s_l2};
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.nsel) return;
+  const int c = a.sel[j];
+  const int n = a.ncell, m = a.nsel;
+  SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};
+  St<L> s;
+#pragma unroll
+  for (int p = 0; p < 4; p++)
+#pragma unroll
+    for (int i = 1; i <= L; i++) cs.set_lay(p, i, a.par[(size_t)(p * L + i - 1) * n + c]);
+  cs.set_sc(PS_FMAX, a.par[(size_t)(4 * L) * n + c]);
+#pragma unroll
+  for (int i = 1; i <= L; i++) {
+    s.h2o[i] = a.st[(size_t)(0 * L + i - 1) * m + j];
+    s.smp[i] = a.st[(size_t)(2 * L + i - 1) * m + j];
+    cs.set_lay(PF_ROOTR, i, a.st[(size_t)(3 * L + i - 1) * m + j]);
+  }
+  const float h2o_ma1 = a.st[(size_t)(1 * L) * m + j];
+  const size_t o8 = (size_t)(4 * L + 1) * m + j;
+  s.zwt = a.st[o8 + 0 * (size_t)m];
+  s.wa = a.st[o8 + 1 * (size_t)m];
+  s.LAI = a.st[o8 + 2 * (size_t)m];
+  s.LAI_litter = a.st[o8 + 3 * (size_t)m];
+  s.pm = a.st[o8 + 4 * (size_t)m];
+  s.pfm = a.st[o8 + 5 * (size_t)m];
+  s.plen = a.st[o8 + 6 * (size_t)m];
+  s.rdepth = a.st[o8 + 7 * (size_t)m];
+  s.naq = 0;
+  float ts_sum = zero;
+#pragma unroll
+  for (int i = 1; i <= L; i++) ts_sum = ts_sum + cs.lay(PF_TS, i);
+  if (!(ts_sum > 1.0E-8f) || a.err[c] != 0) {      // masked, or stopped before the run: no line at all
+    size_t d = 0;
+    for (int y = 0; y < a.nyears; y++)
+      for (int k = 0; k < a.yrs[y].nt; k++, d++)
+        for (int r = 0; r < 11; r++) a.out[(d * 11 + r) * m + j] = __builtin_nanf("");
+    return;
+  }
+  cell_inv_pair<L, G>(g, cs);
+  cell_focus<L, G, SS>(g, cs, s, h2o_ma1, a.yrs, a.nyears, (size_t)c, (size_t)n, a.fvar, a.nisurf, a.grow_on,
+                       a.out + j, (size_t)m, T);
+}
+
 template <int L, class G>
 __global__ void __launch_bounds__(H9G_BLOCK) h9g_init_kernel(int ncell, const float *__restrict__ par,
                                                              float *__restrict__ st, const G g) {
@@ -1123,6 +1209,16 @@ struct h9g_ctx {
   int64_t ord_stats[9] = {};      // last ordered call (h9g_ordered_stats)
   int ord_probe = 1;              // the checks' day-1 probe (H9G_NO_PROBE: off)
   std::vector<int64_t> ord_passes;
+  // daily diagnostics (h9g_set_daily / h9g_get_daily; h9g_focus_kernel)
+  std::vector<int> daily_sel;     // the selected cells; empty: off
+  int *d_dsel = nullptr;          // ... on the device
+  float *d_dst = nullptr;         // their gathered start state, state rows of nsel
+  float *d_daily = nullptr;       // the lines of the last call, (days, 11, nsel)
+  size_t daily_cap = 0;           // floats allocated there
+  FocusYear *d_fyrs = nullptr;    // a launch's years (forcing base, days)
+  size_t fyrs_cap = 0;
+  std::vector<FocusYear> h_fyrs;
+  std::vector<int> daily_nt;      // days of each year recorded by the last call
 };
 
 static void ord_free(h9g_ctx *ctx);
@@ -1266,6 +1362,10 @@ void h9g_destroy(h9g_ctx *ctx) {
   (void)hipFree(ctx->d_hist);
   (void)hipFree(ctx->d_aqbits);
   (void)hipFree(ctx->d_pace);
+  (void)hipFree(ctx->d_dsel);
+  (void)hipFree(ctx->d_dst);
+  (void)hipFree(ctx->d_daily);
+  (void)hipFree(ctx->d_fyrs);
   ord_free(ctx);
   for (auto e : ctx->ev_copied) hipEventDestroy(e);
   for (auto e : ctx->ev_consumed) hipEventDestroy(e);
@@ -1310,6 +1410,10 @@ static int l10_kind(size_t n, int ncu, size_t *n_solo) {
 // arrays plus what the first h9g_run_year / h9g_soil_layer allocate lazily
 // (the pair kernel's per-workgroup day-snapshot blocks, the pacing rows, the
 // soil build's slow-cell flags).
+// Not counted: the daily diagnostics of a selection (h9g_set_daily), whose
+// size depends on the call -- years x max_days x 11 x nsel floats for the
+// lines, allocated by the run that records them and kept until the context is
+// destroyed, plus the nsel gathered state rows (H9G_ENOMEM if they do not fit).
 // Device bytes of the ordered mode's buffers for decades of up to ny years
 // (h9g_config_bytes counts them with ny = 10).
 static size_t ord_bytes(size_t n, size_t L, size_t ny) {
@@ -2007,7 +2111,144 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Daily diagnostics of selected cells (h9g_set_daily, h9g_get_daily)
+// ---------------------------------------------------------------------------
+// The year kernels store nothing per day.  The selected cells are run once
+// more by h9g_focus_kernel from a gathered copy of their start state, on the
+// compute stream before the year kernel (h9g_run_year) or after the decade's
+// fixed point has settled (the cell order).  With no selection none of this
+// runs: no launch, allocation or synchronisation.
+
+// Room for the lines of years jyear0 .. jyear0+nyears-1; nothing recorded yet.
+static int daily_begin(h9g_ctx *ctx, int jyear0, int nyears) {
+  ctx->daily_nt.clear();
+  size_t days = 0;
+  for (int y = 0; y < nyears; y++) days += (size_t)days_in_year(jyear0 + y);
+  const size_t need = days * H9G_NDAILY * ctx->daily_sel.size();
+  if (ctx->daily_cap < need || ctx->fyrs_cap < (size_t)nyears) HIPCHK(hipStreamSynchronize(ctx->sc));
+  if (ctx->daily_cap < need) {
+    (void)hipFree(ctx->d_daily);
+    ctx->d_daily = nullptr;
+    ctx->daily_cap = 0;
+    if (hipMalloc(&ctx->d_daily, sizeof(float) * need) != hipSuccess) {
+      (void)hipGetLastError();
+      return H9G_ENOMEM;
+    }
+    ctx->daily_cap = need;
+  }
+  if (ctx->fyrs_cap < (size_t)nyears) {
+    (void)hipFree(ctx->d_fyrs);
+    ctx->d_fyrs = nullptr;
+    ctx->fyrs_cap = 0;
+    if (hipMalloc(&ctx->d_fyrs, sizeof(FocusYear) * (size_t)nyears) != hipSuccess) {
+      (void)hipGetLastError();
+      return H9G_ENOMEM;
+    }
+    ctx->fyrs_cap = (size_t)nyears;
+  }
+  ctx->h_fyrs.resize(std::max(ctx->h_fyrs.size(), (size_t)nyears));
+  return 0;
+}
+
+// The selected cells over years jyear0 .. jyear0+ny-1 (forcing in slots[0..ny),
+// already waited for on the compute stream) from the state rows st (stride
+// ncell), smp from guess where given, STOP records err; appended to the lines
+// recorded since daily_begin.
+static int daily_launch(h9g_ctx *ctx, const float *st, const float *guess, const int *err, const int32_t *slots,
+                        int jyear0, int ny) {
+  const int nsel = (int)ctx->daily_sel.size(), n = (int)ctx->n, L = ctx->L;
+  const size_t k0 = ctx->daily_nt.size();
+  size_t day0 = 0, days = 0;
+  for (int nt : ctx->daily_nt) day0 += (size_t)nt;
+  if (k0 + (size_t)ny > ctx->fyrs_cap || k0 + (size_t)ny > ctx->h_fyrs.size()) return H9G_ESTATE;
+  for (int y = 0; y < ny; y++) {
+    const int nt = days_in_year(jyear0 + y);
+    if (slots[y] < 0 || slots[y] >= ctx->cfg.nslots || ctx->slot_days[slots[y]] < nt) return H9G_EINVAL;
+    ctx->h_fyrs[k0 + y].forc = h9g_forcing_slot(ctx, slots[y]);
+    ctx->h_fyrs[k0 + y].nt = nt;
+    days += (size_t)nt;
+  }
+  if ((day0 + days) * H9G_NDAILY * (size_t)nsel > ctx->daily_cap) return H9G_ESTATE;
+  HIPCHK(hipMemcpyAsync(ctx->d_fyrs + k0, ctx->h_fyrs.data() + k0, sizeof(FocusYear) * (size_t)ny,
+                        hipMemcpyHostToDevice, ctx->sc));
+  h9g_focus_gather_kernel<<<(unsigned)((nsel + 255) / 256), 256, 0, ctx->sc>>>(nsel, n, h9g_state_size(L), L, ctx->d_dsel,
+                                                                              st, guess, ctx->d_dst);
+  HIPCHK(hipGetLastError());
+  FocusArgs a;
+  a.ncell = n;
+  a.nsel = nsel;
+  a.nyears = ny;
+  a.nisurf = ctx->cfg.nisurf;
+  a.grow_on = ctx->cfg.grow_on;
+  a.fvar = (size_t)ctx->cfg.max_days * ctx->n;
+  a.par = ctx->d_par;
+  a.st = ctx->d_dst;
+  a.sel = ctx->d_dsel;
+  a.err = err;
+  a.yrs = ctx->d_fyrs + k0;
+  a.out = ctx->d_daily + day0 * H9G_NDAILY * (size_t)nsel;
+  H9G_DISPATCH(ctx, h9g_focus_kernel, (unsigned)((nsel + 63) / 64), 64, ctx->sc, a);
+  HIPCHK(hipGetLastError());
+  for (int y = 0; y < ny; y++) ctx->daily_nt.push_back(days_in_year(jyear0 + y));
+  return 0;
+}
+
+// h9g_run_year's shadow run: the selected cells from the context's state as
+// the year kernel is about to find it.
+static int daily_year(h9g_ctx *ctx, int slot, int jyear) {
+  if (slot < 0 || slot >= ctx->cfg.nslots || jyear < 1861 || jyear > 2299) return H9G_EINVAL;
+  if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
+  if (const int prc = join_prefetch(ctx, slot)) return prc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int r = daily_begin(ctx, jyear, 1)) return r;
+  HIPCHK(hipStreamWaitEvent(ctx->sc, ctx->ev_copied[slot], 0));
+  const int32_t s = slot;
+  return daily_launch(ctx, ctx->d_st, nullptr, ctx->d_err, &s, jyear, 1);
+}
+
+int h9g_set_daily(h9g_ctx *ctx, int nsel, const int32_t *cells) {
+  if (!ctx || nsel < 0 || (nsel > 0 && !cells) || (size_t)nsel > ctx->n) return H9G_EINVAL;
+  for (int j = 0; j < nsel; j++)
+    if (cells[j] < 0 || (size_t)cells[j] >= ctx->n || (j > 0 && cells[j] <= cells[j - 1])) return H9G_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  (void)hipFree(ctx->d_dsel);
+  (void)hipFree(ctx->d_dst);
+  ctx->d_dsel = nullptr;
+  ctx->d_dst = nullptr;
+  ctx->daily_sel.clear();
+  ctx->daily_nt.clear();
+  if (nsel == 0) return 0;
+  if (hipMalloc(&ctx->d_dsel, sizeof(int) * (size_t)nsel) != hipSuccess ||
+      hipMalloc(&ctx->d_dst, sizeof(float) * (size_t)h9g_state_size(ctx->L) * (size_t)nsel) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(ctx->d_dsel);
+    ctx->d_dsel = nullptr;
+    return H9G_ENOMEM;
+  }
+  HIPCHK(hipMemcpy(ctx->d_dsel, cells, sizeof(int) * (size_t)nsel, hipMemcpyHostToDevice));
+  ctx->daily_sel.assign(cells, cells + nsel);
+  return 0;
+}
+
+int h9g_get_daily(h9g_ctx *ctx, int k, float *out) {
+  if (!ctx || !out) return H9G_EINVAL;
+  if (ctx->daily_sel.empty() || ctx->daily_nt.empty()) return H9G_ESTATE;
+  if (k < 0 || (size_t)k >= ctx->daily_nt.size()) return H9G_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  size_t day0 = 0;
+  for (int y = 0; y < k; y++) day0 += (size_t)ctx->daily_nt[(size_t)y];
+  const size_t row = (size_t)H9G_NDAILY * ctx->daily_sel.size();
+  HIPCHK(hipMemcpy(out, ctx->d_daily + day0 * row, sizeof(float) * (size_t)ctx->daily_nt[(size_t)k] * row,
+                   hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int h9g_run_year(h9g_ctx *ctx, int slot, int jyear) {
+  if (ctx && !ctx->daily_sel.empty())
+    if (int r = daily_year(ctx, slot, jyear)) return r;
   YearSpec ys;
   ys.slot = slot;
   ys.jyear = jyear;
@@ -2526,6 +2767,13 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
   if (int r = ord_finish(ctx, *P, nullptr, annual, stop_seen)) return r;
   S.dec_passes.push_back(P->np);
   S.passes += P->np;
+  // daily diagnostics (h9g_set_daily): the decade has settled, so guess holds
+  // the smp every chain cell's first substep reads; the selected cells run the
+  // decade once more from its start (st0, err0) with that input
+  if (!ctx->daily_sel.empty()) {
+    if (decs.size() != 1) return H9G_EINVAL;   // (h9g_run_ordered runs its decades one by one then)
+    if (int r = daily_launch(ctx, P->st0, P->guess, P->err0, slots + P->k0, P->y0, P->ny)) return r;
+  }
   // the last decade's end: the context's state, STOP records and last-year means
   HIPCHK(hipMemcpyAsync(ctx->d_st, ord_ck(ctx, *P, P->ny - 1), sizeof(float) * srows * n, hipMemcpyDeviceToDevice,
                         ctx->sc));
@@ -2565,11 +2813,38 @@ static std::vector<std::pair<int, int>> ref_decades(int jyear0, int nyears) {
 
 int h9g_run_decade_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, float *annual, int32_t *passes) {
   if (nyears < 1) return H9G_EINVAL;
+  if (ctx && !ctx->daily_sel.empty()) {
+    if (jyear0 < 1861 || jyear0 + nyears - 1 > 2299) return H9G_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int r = daily_begin(ctx, jyear0, nyears)) return r;
+  }
   return run_ordered_impl(ctx, slots, jyear0, {{jyear0, nyears}}, annual, passes);
 }
 
 int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, float *annual, int32_t *passes) {
   if (nyears < 1 || jyear0 < 1861) return H9G_EINVAL;
+  if (ctx && !ctx->daily_sel.empty()) {
+    // with a selection the decades run one after another, each as
+    // h9g_run_decade_ordered runs it (the same results bit for bit), and each
+    // replays the selected cells once it has settled
+    if (!slots || jyear0 + nyears - 1 > 2299) return H9G_EINVAL;
+    std::vector<char> used((size_t)ctx->cfg.nslots, 0);
+    for (int y = 0; y < nyears; y++)
+      if (slots[y] < 0 || slots[y] >= ctx->cfg.nslots || used[(size_t)slots[y]]++) return H9G_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int r = daily_begin(ctx, jyear0, nyears)) return r;
+    const size_t rows = 12 + (size_t)ctx->L;
+    int first = 0, k0 = 0, i = 0;
+    for (const auto &d : ref_decades(jyear0, nyears)) {
+      const int r = run_ordered_impl(ctx, slots + k0, d.first, {d}, annual ? annual + (size_t)k0 * rows * ctx->n : nullptr,
+                                     passes ? passes + i : nullptr);
+      if (r < 0) return r;
+      if (r > 0 && !first) first = r;
+      k0 += d.second;
+      i++;
+    }
+    return first;
+  }
   return run_ordered_impl(ctx, slots, jyear0, ref_decades(jyear0, nyears), annual, passes);
 }
 

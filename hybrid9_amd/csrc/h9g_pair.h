@@ -2447,4 +2447,80 @@ H9K_HD int cell_site(const G &g, CS cs, St<L> &s, float h2o_ma1, const float *su
   return 0;
 }
 
+// The daily diagnostics line of the reference's INTERACTIVE mode
+// (HYBRID9.f90:221-229) for one grid cell: a shadow run of the cell's years
+// from a copy of its start state, beside the year kernels and not inside
+// them.  Every kernel computes the reference's bits, so this run follows the
+// trajectory the year kernel takes.  As cell_site it runs every substep on
+// the exact path with one lane for all layers (the fast path's exact re-run
+// restores state from the day snapshot and does not carry the fluxes), but
+// on the PGF day forcing and with GROW, as cell_year_pair: make_day,
+// day_consts, nisurf substeps, grow_day when grow_on.  It reads only:
+// no state, annual mean or STOP record is stored.
+//   yrs   the consecutive calendar years: forcing base (7 variables fvar
+//         apart, days fday apart, this cell at `cell`) and days
+//   out   (total days, 11, n): evap_day, evap_grnd_day, theta(1:4),
+//         theta_ma(1), LAI, LAI_litter (after GROW), w_i, fT (as GROW computed
+//         them that day, GROW.f90:55-71; 0 when grow_on = 0)             :223-228
+// A cell that reaches a reference STOP has NaN from that day on (the
+// reference ends before writing the day's line); returns its code.
+struct FocusYear {
+  const float *forc;
+  int nt;
+};
+
+template <int L, class G, class CS>
+H9K_HD int cell_focus(const G &g, CS cs, St<L> &s, float h2o_ma1, const FocusYear *yrs, int nyears, size_t cell,
+                      size_t fday, size_t fvar, int nisurf, int grow_on, float *out, size_t n,
+                      const h9m::Tabs &T) {
+  MathExact me{T};
+  const SplitAll sp;
+  FluxProf fx{zero, zero};
+  float rnf_sum = zero, errval = zero, npp = zero;
+  const float dt = g.dt();
+  const float theta_ma1 = h2o_ma1 / g.thk(1);                         // HYDROLOGY.f90:149
+  const float nan = __builtin_nanf("");
+  gbl_float *o = (gbl_float *)out;
+  int code = 0;
+  for (int y = 0; y < nyears; y++) {
+    const gbl_float *forc = (const gbl_float *)yrs[y].forc + cell;
+    const int nt = yrs[y].nt;
+    for (int day = 0; day < nt; day++, o += 11 * n) {
+      float evap_day = zero, evap_grnd_day = zero, w_i = zero, fT = zero;
+      if (!code) {
+        const gbl_float *f = forc + (size_t)day * fday;
+        float fv[7];             // tas rlds rsds huss ps pr rhs
+#pragma unroll
+        for (int k = 0; k < 7; k++) fv[k] = ld_stream(f + k * fvar);
+        const Day d = make_day(fv[0], fv[1], fv[2], fv[3], fv[4], fv[5], fv[6]);   // :168-184
+        day_consts(d, s.LAI, s.LAI_litter, cs, me);
+        for (int ns = 0; ns < nisurf && !code; ns++) {                  // :193-211
+          code = hydrology_pair<L, G, MathExact, SplitAll, CS, FluxProf>(g, cs, sp, s, rnf_sum, errval, me, fx);
+          evap_day = evap_day + (fx.evg + fx.tran) * dt;                // :207-209
+          evap_grnd_day = evap_grnd_day + fx.evg * dt;
+        }
+        if (!code && grow_on) {
+          grow_drivers<L>(fv[0], s, cs, w_i, fT);
+          grow_day<L, G, MathExact>(g, fv[0], s, cs, npp, me);          // :217
+        }
+      }
+      if (code) {
+#pragma unroll
+        for (int r = 0; r < 11; r++) o[r * n] = nan;
+        continue;
+      }
+      o[0] = evap_day;
+      o[n] = evap_grnd_day;
+#pragma unroll
+      for (int i = 1; i <= 4; i++) o[(1 + i) * n] = MAXF(s.h2o[i], 1.0E-6f) / g.thk(i);   // :1233
+      o[6 * n] = theta_ma1;
+      o[7 * n] = s.LAI;
+      o[8 * n] = s.LAI_litter;
+      o[9 * n] = w_i;
+      o[10 * n] = fT;
+    }
+  }
+  return code;
+}
+
 }  // namespace h9k

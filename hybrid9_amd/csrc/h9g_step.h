@@ -520,6 +520,31 @@ H9K_HD void grow_day(const G &g, float tas, St<L> &s, const CS &cs, float &npp, 
   s.LAI_litter = s.LAI_litter - 0.02f * s.LAI_litter;
 }
 
+// GROW.f90:55-71: the water and temperature factors grow_day is about to
+// compute from this state, by the same expressions in the same order.  The
+// daily diagnostics line reports them (cell_focus, h9g_pair.h); grow_day
+// itself is left as it is, so the year kernels compile exactly as before.
+template <int L, class CS>
+H9K_HD void grow_drivers(float tas, const St<L> &s, const CS &cs, float &w_i, float &fT) {
+  w_i = zero;
+#pragma unroll
+  for (int i = 1; i <= L; i++) {
+    float w = (-150000.0f - s.smp[i]) / (-150000.0f - (-50000.0f));
+    w = MAXF(zero, w);
+    w = MINF(one, w);
+    w_i = w_i + cs.root(i) * w;
+  }
+  if ((tas - tf) > 18.0f) {
+    const float a = absf(tas - tf - 18.0f) / 21.0f;
+    fT = one - a * a;
+  } else {
+    const float a = absf(tas - tf - 18.0f) / 25.0f;
+    fT = one - a * a;
+    fT = MAXF(zero, fT);
+    fT = MINF(one, fT);
+  }
+}
+
 // INIT.f90:707-811 for one cell (smp = 0).
 template <int L, class G, class M>
 H9K_HD void init_cell(const G &g, const float *ts, St<L> &s, float *rootr, float *h2o_ma, M &m) {

@@ -14,6 +14,7 @@ IMPLICIT NONE
 
 INTEGER, PARAMETER :: H9G_LMAX = 10
 INTEGER, PARAMETER :: H9G_NDIAG = 12
+INTEGER, PARAMETER :: H9G_NDAILY = 11
 INTEGER, PARAMETER :: H9G_ERR_TRIDIAG1 = 1, H9G_ERR_TRIDIAG2 = 2
 INTEGER, PARAMETER :: H9G_ERR_RSUB_POS = 3, H9G_ERR_IMBALANCE = 4
 INTEGER, PARAMETER :: H9G_ERR_NOSNAP = 5   ! internal invariant, not a reference STOP
@@ -321,6 +322,23 @@ INTERFACE
     INTEGER(C_INT), VALUE :: nday
     REAL(C_FLOAT) :: sub (*), daily (*), lai (*), diag (*)
     INTEGER(C_INT) :: h9g_run_site
+  END FUNCTION
+  ! Daily diagnostics of selected cells (HYBRID9.f90:221-229): cells(nsel)
+  ! are 0-based context indices, strictly increasing; nsel = 0 turns it off.
+  FUNCTION h9g_set_daily (ctx, nsel, cells) BIND(C, NAME='h9g_set_daily')
+    IMPORT :: C_PTR, C_INT, C_INT32_T
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: nsel
+    INTEGER(C_INT32_T), INTENT(IN) :: cells (*)
+    INTEGER(C_INT) :: h9g_set_daily
+  END FUNCTION
+  ! The lines of year k (0-based) of the last run: out (nsel, 11, nday_k).
+  FUNCTION h9g_get_daily (ctx, k, out) BIND(C, NAME='h9g_get_daily')
+    IMPORT :: C_PTR, C_INT, C_FLOAT
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: k
+    REAL(C_FLOAT) :: out (*)
+    INTEGER(C_INT) :: h9g_get_daily
   END FUNCTION
   FUNCTION h9g_last_kernel_ms (ctx) BIND(C, NAME='h9g_last_kernel_ms')
     IMPORT :: C_PTR, C_FLOAT

@@ -33,6 +33,16 @@ PROGRAM H9_HOST
 ! 0 (default) makes one call.  cell_order = 0: every cell its own smp
 ! (h9g_run_year per year, isolated-cell semantics, DESIGN.md §1).
 !
+! daily = 1 records the daily diagnostics line (HYBRID9.f90:221-229) of
+! every cell of the run (h9g_set_daily, DESIGN.md §7) and writes them to
+! <out_dir>/daily.f32 as (ncell, 11, total days); the cell order then runs
+! decade by decade through h9g_run_decade_ordered.  INTERACTIVE = .T. in
+! driver.txt, on a grid (synth/pgf), is the reference's focus window
+! (INIT.f90:220-236, 280-283, 462-466): the land list is cut to the window
+! of lon_c_w x lat_c_w cells from (lon_w, lat_w), all of them recorded, and
+! LCLIM/daily_diag.csv is written under the working directory with the
+! reference's header, format and order (decade, cell, year, day).
+!
 ! Usage:  h9_host [driver.txt] [h9gpu.nml]
 ! Outputs: <out_dir>/annual.f32 (ncell, 12+L, nyears),
 !          <out_dir>/state_end.f32 (packed state, include/h9g.h) and, on a
@@ -53,11 +63,11 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 ! --- extension namelist ----------------------------------------------------
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
-INTEGER :: cell_order, ordered_decades
+INTEGER :: cell_order, ordered_decades, daily
 INTEGER(C_INT64_T) :: seed
 NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
-                 cell_order, ordered_decades
+                 cell_order, ordered_decades, daily
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
 TYPE(C_PTR) :: pgf_ptr (7)
 CHARACTER (LEN = *), PARAMETER :: pgf_var (7) = &
@@ -85,6 +95,12 @@ REAL(C_FLOAT), ALLOCATABLE :: lat (:)
 REAL(C_DOUBLE) :: diag (H9G_NDIAG)
 TYPE(h9g_error) :: err
 INTEGER :: time_BOY (2300-1860+1)
+! --- daily diagnostics (h9g_set_daily): the current decade's lines ---------
+INTEGER(C_INT32_T), ALLOCATABLE :: dcells (:)
+REAL(C_FLOAT), ALLOCATABLE :: dbuf (:,:,:)
+INTEGER, ALLOCATABLE :: dyear (:)
+INTEGER :: dfill, dnyr, udaily, ucsv, lon_s_w, lat_s_w, nwin, ix, iy
+REAL :: a_lon, b_lon, a_lat, b_lat, lon1, lat1
 
 !----------------------------------------------------------------------!
 ! Defaults, then driver.txt and h9gpu.nml.
@@ -92,6 +108,7 @@ INTEGER :: time_BOY (2300-1860+1)
 input_mode = 'synth'; case_dir = ''; out_dir = '.'; pgf_dir = '.'
 nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
+daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
 PATH_output = '.'
 seed = 20161123_C_INT64_T
 NISURF = 48; iDEC_start = 1; iDEC_end = 1
@@ -175,6 +192,37 @@ ELSE
   ALLOCATE (gid (ncell), lat (ncell))
   rc = h9g_land_cells (nx, ny, nland, seed, gid, lat)
   IF (rc /= 0) STOP 'h9_host: h9g_land_cells failed'
+  IF (INTERACTIVE) THEN
+    ! the focus window (INIT.f90:220-236): the reference's linear maps from
+    ! degrees to 1-based indices, its +-179.75 / +-89.75 cell centres written
+    ! for any grid; then lon_c = lon_c_w, lat_c = lat_c_w, lon_s = lon_s_w,
+    ! lat_s = lat_s_w (:280-283, :462-466) cut the land list to the window
+    lon1 = 180.0 - 180.0 / FLOAT (nx)
+    lat1 = 90.0 - 90.0 / FLOAT (ny)
+    b_lon = (FLOAT (nx) - 1.0) / (lon1 - (-lon1))
+    a_lon = 1.0 - b_lon * (-lon1)
+    b_lat = (FLOAT (ny) - 1.0) / (-lat1 - lat1)
+    a_lat = FLOAT (ny) - b_lat * (-lat1)
+    lon_s_w = NINT (a_lon + b_lon * lon_w)
+    lat_s_w = NINT (a_lat + b_lat * lat_w)
+    WRITE (*,*) 'Details of focus point', lon_w, lat_w, lon_s_w, lat_s_w
+    nwin = 0
+    DO i = 1, ncell
+      ix = INT (MOD (gid (i), INT (nx, C_INT64_T))) + 1
+      iy = INT (gid (i) / INT (nx, C_INT64_T)) + 1
+      IF (ix >= lon_s_w .AND. ix < lon_s_w + NINT (lon_c_w) .AND. &
+          iy >= lat_s_w .AND. iy < lat_s_w + NINT (lat_c_w)) THEN
+        nwin = nwin + 1
+        gid (nwin) = gid (i)
+        lat (nwin) = lat (i)
+      END IF
+    END DO
+    IF (nwin == 0) STOP 'h9_host: INTERACTIVE: the focus window holds no land cell'
+    ncell = nwin
+    gid = gid (1:ncell)
+    lat = lat (1:ncell)
+    daily = 1
+  END IF
   IF (year0 == 0) year0 = (iDEC_start - 1) * 10 + 1901        ! HYBRID9.f90:103
   IF (nyears == 0) THEN                                        ! HYBRID9.f90:109-113
     eyr = (iDEC_end - 1) * 10 + 1901 + MERGE (9, 1, iDEC_end < 12)
@@ -193,6 +241,7 @@ END DO
 nslot = 2                                  ! isolated cells: double-buffered years
 IF (cell_order /= 0) THEN                  ! the reference's order: every year of a call resident
   nslot = nyears
+  IF (daily /= 0) ordered_decades = 1      ! recorded runs: one h9g_run_decade_ordered per decade
   IF (ordered_decades > 0) nslot = MIN (nyears, 10 * ordered_decades)
 END IF
 cfg%ncell = ncell
@@ -233,6 +282,23 @@ END IF
 ALLOCATE (annual (ncell, 12 + L))
 OPEN (NEWUNIT = u, FILE = TRIM (out_dir)//'/annual.f32', ACCESS = 'STREAM', &
       FORM = 'UNFORMATTED', STATUS = 'REPLACE')
+IF (daily /= 0) THEN
+  ALLOCATE (dcells (ncell), dbuf (ncell, H9G_NDAILY, 366 * MIN (nyears, 10)), dyear (10))
+  DO i = 1, ncell
+    dcells (i) = i - 1
+  END DO
+  CALL chk (h9g_set_daily (ctx, ncell, dcells))
+  dfill = 0; dnyr = 0
+  OPEN (NEWUNIT = udaily, FILE = TRIM (out_dir)//'/daily.f32', ACCESS = 'STREAM', &
+        FORM = 'UNFORMATTED', STATUS = 'REPLACE')
+  IF (INTERACTIVE) THEN                      ! INIT.f90:887-890
+    CALL EXECUTE_COMMAND_LINE ('mkdir -p LCLIM')
+    OPEN (NEWUNIT = ucsv, FILE = 'LCLIM/daily_diag.csv', STATUS = 'UNKNOWN')
+    WRITE (ucsv,'(A200)') 'jyear,  DOY,  et,  et_g,  theta_1,  theta_2,  &
+                  &theta_3,  theta_4,&
+                  &  theta_ma_1,  lai,  lai_litter, w_i, fT'
+  END IF
+END IF
 d0 = 1
 IF (cell_order /= 0) THEN
   ! HYBRID9.f90:93-130: decade by decade (1901-1910, 1911-1920, ...), cut to
@@ -253,8 +319,18 @@ IF (cell_order /= 0) THEN
       CALL stage (k - 1, dsyr + k - 1, d0)
       d0 = d0 + time_BOY (dsyr+k-1859) - time_BOY (dsyr+k-1-1859)
     END DO
-    rc = h9g_run_ordered (ctx, slots, dsyr, ndec, annual_dec, passes)
+    IF (daily /= 0) THEN                     ! (one reference decade per call)
+      rc = h9g_run_decade_ordered (ctx, slots, dsyr, ndec, annual_dec, passes (1))
+    ELSE
+      rc = h9g_run_ordered (ctx, slots, dsyr, ndec, annual_dec, passes)
+    END IF
     IF (rc < 0) CALL h9g_check_stop (ctx, rc)
+    IF (daily /= 0) THEN
+      DO k = 1, ndec
+        CALL daily_year (k - 1, dsyr + k - 1)
+      END DO
+      CALL daily_flush ()
+    END IF
     iyr = ndec
     IF (rc > 0) THEN                         ! a STOP: the reference ends in its decade,
       CALL chk (h9g_last_error (ctx, err))   ! after writing the decades before it
@@ -280,10 +356,18 @@ DO iyr = 1, nyears
   CALL h9g_check_stop (ctx, rc)
   CALL chk (h9g_get_annual (ctx, annual))
   CALL year_out (jyear)
+  IF (daily /= 0) THEN                       ! flushed at the end of each reference decade
+    CALL daily_year (0, jyear)
+    IF (MODULO (jyear - 1900, 10) == 0 .OR. iyr == nyears) CALL daily_flush ()
+  END IF
   d0 = d0 + nt
 END DO
 END IF
 CLOSE (u)
+IF (daily /= 0) THEN
+  CLOSE (udaily)
+  IF (INTERACTIVE) CLOSE (ucsv)
+END IF
 ALLOCATE (state (h9g_state_size (L) * ncell))
 CALL chk (h9g_get_state (ctx, state))
 OPEN (NEWUNIT = u, FILE = TRIM (out_dir)//'/state_end.f32', ACCESS = 'STREAM', &
@@ -309,6 +393,43 @@ CONTAINS
           ' mean runoff', diag (2) / MAX (diag (1), 1.0D0), ' mm/s  mean soil water', &
           diag (3) / MAX (diag (1), 1.0D0), ' mm  (', h9g_last_kernel_ms (ctx), ' ms)'
   END SUBROUTINE year_out
+
+  ! The daily lines of year k (0-based) of the last run, calendar year y,
+  ! appended to the current decade's.
+  SUBROUTINE daily_year (k, y)
+    INTEGER, INTENT(IN) :: k, y
+    INTEGER :: n
+    n = time_BOY (y+1-1859) - time_BOY (y-1859)
+    CALL chk (h9g_get_daily (ctx, k, dbuf (:, :, dfill+1:dfill+n)))
+    dnyr = dnyr + 1
+    dyear (dnyr) = y
+    dfill = dfill + n
+  END SUBROUTINE daily_year
+
+  ! The decade's lines to daily.f32 (cell fastest, 11, days) and, in the
+  ! reference's order (cell, year, day; HYBRID9.f90:120-229), to
+  ! LCLIM/daily_diag.csv.  A cell's lines from its STOP on are NaN: the
+  ! reference ends before writing them.
+  SUBROUTINE daily_flush ()
+    INTEGER :: c, j, d, doy, n, i
+    IF (dfill == 0) RETURN
+    WRITE (udaily) dbuf (:, :, 1:dfill)
+    IF (INTERACTIVE) THEN
+      DO c = 1, ncell
+        d = 0
+        DO j = 1, dnyr
+          n = time_BOY (dyear (j)+1-1859) - time_BOY (dyear (j)-1859)
+          DO doy = 1, n
+            d = d + 1
+            IF (dbuf (c, 1, d) /= dbuf (c, 1, d)) CYCLE
+            WRITE (ucsv,'(2(I5,A1),10(F10.4,A1),F10.4)') dyear (j), ',', doy, ',', &
+                  (dbuf (c, i, d), ',', i = 1, 10), dbuf (c, 11, d)
+          END DO
+        END DO
+      END DO
+    END IF
+    dfill = 0; dnyr = 0
+  END SUBROUTINE daily_flush
 
   SUBROUTINE chk (r)
     INTEGER(C_INT), INTENT(IN) :: r

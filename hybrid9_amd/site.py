@@ -25,7 +25,10 @@ from . import synth
 
 DIAG_FIELDS = ("evap_day", "evap_grnd_day", "theta1", "theta2", "theta3", "theta4",
                "theta_ma1", "LAI", "LAI_litter", "w_i", "fT")      # HYBRID9.f90:464-469
-SUB_COLUMNS = (22, 25, 14, 16, 35)     # LCLIM_array2 columns of tak, rh, Rnet, PAR, ppt (:430-435)
+# header of LCLIM/daily_diag.csv (INIT.f90:888-890; format A200 right-justifies it)
+DAILY_HEADER = ("jyear,  DOY,  et,  et_g,  theta_1,  theta_2,  theta_3,  theta_4,"
+                "  theta_ma_1,  lai,  lai_litter, w_i, fT").rjust(200)
+SUB_COLUMNS = (22, 25, 14, 16, 35)    # LCLIM_array2 columns of tak, rh, Rnet, PAR, ppt (:430-435)
 DAILY_COLUMNS = (5, 6)                 # LCLIM_array columns of huss, ps (:377-378)
 NAN = np.float32(np.nan)
 
@@ -116,6 +119,54 @@ def write_daily_csv(path, diag, years, cell: int = 0, nloop: int = 1):
                     v = ",".join("%10.4f" % x for x in diag[k, :, cell])
                     f.write("%5d,%5d,%s\n" % (y, doy, v))
                     k += 1
+
+
+def focus_window(lon_w, lat_w, lon_c_w: int, lat_c_w: int, nx: int = 720, ny: int = 360):
+    """The reference's INTERACTIVE focus window (INIT.f90:220-236, 280-283,
+    462-466): the 1-based grid indices (lon_s_w, lat_s_w) of the focus point
+    (lon_w, lat_w) in degrees, by the reference's linear maps in REAL
+    arithmetic and NINT, and the grid ids (iy*nx + ix, row 0 north) of the
+    lon_c_w x lat_c_w cells from there, in the reference's (y, x) order.
+    Returns (lon_s_w, lat_s_w, gids).  The cell centres run from -180 + 180/nx
+    to 180 - 180/nx (the reference's +-179.75 at nx = 720) and from 90 - 90/ny
+    down to -90 + 90/ny.  Cells past the grid's edge are left out."""
+    f = np.float32
+    lon1, lat1 = f(180.0) - f(180.0) / f(nx), f(90.0) - f(90.0) / f(ny)
+    b_lon = (f(nx) - f(1.0)) / (lon1 - (-lon1))
+    a_lon = f(1.0) - b_lon * (-lon1)
+    b_lat = (f(ny) - f(1.0)) / (-lat1 - lat1)
+    a_lat = f(ny) - b_lat * (-lat1)
+
+    def nint(v):                           # Fortran NINT: halves away from zero
+        return int(np.floor(abs(v) + f(0.5))) * (1 if v >= 0 else -1)
+
+    lon_s_w = nint(a_lon + b_lon * f(lon_w))
+    lat_s_w = nint(a_lat + b_lat * f(lat_w))
+    gids = [(y - 1) * nx + (x - 1)
+            for y in range(lat_s_w, lat_s_w + int(lat_c_w)) for x in range(lon_s_w, lon_s_w + int(lon_c_w))
+            if 1 <= y <= ny and 1 <= x <= nx]
+    return lon_s_w, lat_s_w, np.asarray(gids, dtype=np.int64)
+
+
+def write_window_csv(path, daily, years_by_decade, ncell: int):
+    """LCLIM/daily_diag.csv of an INTERACTIVE grid run: the reference's header
+    (INIT.f90:888-890) and its lines (HYBRID9.f90:223-228, format
+    (2(I5,A1),10(F10.4,A1),F10.4)) in its order decade -> cell -> year -> day.
+    daily: (days of all years, 11, ncell); years_by_decade: a list of year
+    lists.  A cell's NaN lines (from its STOP on, or masked) are not written."""
+    with open(path, "w") as f:
+        f.write(DAILY_HEADER + "\n")
+        d0 = 0
+        for years in years_by_decade:
+            nd = sum(synth.days_in_year(y) for y in years)
+            for c in range(ncell):
+                k = d0
+                for y in years:
+                    for doy in range(1, synth.days_in_year(y) + 1):
+                        if not np.isnan(daily[k, 0, c]):
+                            f.write("%5d,%5d,%s\n" % (y, doy, ",".join("%10.4f" % x for x in daily[k, :, c])))
+                        k += 1
+            d0 += nd
 
 
 # -------------------------------------------------------------------------

@@ -223,6 +223,35 @@ int h9g_ordered_stats(h9g_ctx *ctx, int64_t *out, int n);
 int h9g_run_site(h9g_ctx *ctx, int nday, const float *sub, const float *daily,
                  const float *lai, float *diag);
 
+/* --- daily diagnostics of a focus window (HYBRID9.f90:221-229) ---------- */
+/* The line the reference writes to LCLIM/daily_diag.csv each day when
+ * INTERACTIVE is set: evap_day, evap_grnd_day, theta(1:4), theta_ma(1), LAI,
+ * LAI_litter, w_i, fT (jyear and DOY are the caller's).  The year kernels
+ * store nothing per day; the selected cells are run a second time by a small
+ * shadow kernel from the same start state and forcing, which follows the
+ * year kernel's trajectory bit for bit.  It only reads: state,
+ * annual means and STOP records are the same with or without a selection.
+ * A cell that STOPs has NaN from the STOP day on; a masked cell, or one that
+ * had stopped before the run, on every day.  With grow_on = 0, w_i = fT = 0. */
+#define H9G_NDAILY 11
+/* Selects the cells whose daily line later runs record: cells[0..nsel) are
+ * context indices, strictly increasing.  nsel = 0 turns it off (the
+ * default).  H9G_EINVAL for a bad list, H9G_ENOMEM if the buffers do not
+ * fit.  h9g_run_year then launches the shadow run on the compute stream
+ * before its year kernel; h9g_run_decade_ordered replays the selected cells
+ * over the decade once its fixed point has settled, each from its decade
+ * start with the smp its predecessor in the chain hands it; h9g_run_ordered
+ * then runs its decades one after another (no overlap; the same results bit
+ * for bit, h9g_ordered_stats reports the last decade only).  The lines take
+ * nyears x max_days x 11 x nsel floats of device memory, allocated by the
+ * run and released with the context (not part of h9g_config_bytes). */
+int h9g_set_daily(h9g_ctx *ctx, int nsel, const int32_t *cells);
+/* Daily lines of year k (0-based) of the last h9g_run_year (k = 0),
+ * h9g_run_decade_ordered or h9g_run_ordered call: out (nday_k, 11, nsel),
+ * selection order.  Synchronises.  H9G_ESTATE if nothing was recorded,
+ * H9G_EINVAL for a bad k. */
+int h9g_get_daily(h9g_ctx *ctx, int k, float *out);
+
 /* --- outputs (HYBRID9.f90:263-290) ------------------------------------ */
 /* Annual means of the last year run, (12+L) rows of (ncell):
  * npp plant_mass rnf evap tas rlds rsds huss ps pr rhs theta(1..L)
