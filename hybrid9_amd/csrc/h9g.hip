@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -44,11 +45,13 @@
 #include "h9g_geo.h"
 #include "h9g_step.h"
 #include "h9g_pair.h"
+#include "h9g_rows.h"
 #include "h9g_synth.h"
 #include "h9g_io.h"
 
 using namespace h9k;
 static_assert(H9G_ERR_NOSNAP_K == H9G_ERR_NOSNAP, "kernel and ABI error codes");
+static_assert(H9G_NDAILY == DAILY_ROWS, "the daily line of the ABI and of h9g_rows.h");
 
 __constant__ uint64_t c_exp2tab[32] = H9M_EXP2F_TAB_INIT;
 __constant__ double c_log2tab[32] = H9M_POWF_LOG2_TAB_INIT;
@@ -75,11 +78,11 @@ struct KArgs {
   int nisurf;
   int grow_on;
   size_t fvar;     // forcing variable stride (floats) = max_days * ncell
-  const float *__restrict__ par;   // (4L+1) rows x ncell
-  float *__restrict__ st;          // (4L+9) rows x ncell
+  const float *__restrict__ par;   // parameter rows x ncell (h9g_rows.h)
+  float *__restrict__ st;          // state rows x ncell
   const float *__restrict__ forc;  // 7 x max_days x ncell (slot base)
-  float *__restrict__ annual;      // (12+L) rows x ncell
-  int *__restrict__ err;           // 4 rows x ncell: code, day, substep, value bits
+  float *__restrict__ annual;      // annual rows x ncell
+  int *__restrict__ err;           // STOP record rows x ncell
   int *__restrict__ err_flag;
   unsigned *__restrict__ stamps;   // H9G_STAMPS builds: 8 phase cycle sums per wave
   float *__restrict__ sv;          // pair kernel: day snapshot, PairStore::GBLOCK bytes per workgroup
@@ -191,38 +194,25 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g) {
   St<L> s;
   if (!spare) {
 #pragma unroll
-    for (int p = 0; p < 4; p++)
+    for (int p = PF_TS; p <= PF_PSI; p++)
 #pragma unroll
-      for (int t = 0; t < L / 2; t++) cs.set_slot(p, t, a.par[(size_t)(p * L + 2 * t + h) * n + c]);
-    cs.set_sc(PS_FMAX, a.par[(size_t)(4 * L) * n + c]);
+      for (int t = 0; t < L / 2; t++) cs.set_slot(p, t, a.par[(size_t)par_row(L, p, 2 * t + h) * n + c]);
+    cs.set_sc(PS_FMAX, a.par[(size_t)Rows<L>::FMAX * n + c]);
 #pragma unroll
-    for (int t = 0; t < L / 2; t++) cs.set_slot(PF_ROOTR, t, st[(size_t)(3 * L + 2 * t + h) * n + c]);
+    for (int t = 0; t < L / 2; t++) cs.set_slot(PF_ROOTR, t, st[(size_t)rootr_row(L, 2 * t + h) * n + c]);
   }
 #pragma unroll
   for (int i = 1; i <= L; i++) {
-    s.h2o[i] = st[(size_t)(0 * L + i - 1) * n + c];
-    s.smp[i] = st[(size_t)(2 * L + i - 1) * n + c];
+    s.h2o[i] = st[(size_t)(Rows<L>::H2O + i - 1) * n + c];
+    s.smp[i] = st[(size_t)(Rows<L>::SMP + i - 1) * n + c];
   }
-  const size_t o8 = (size_t)(4 * L + 1) * n + c;
-  s.zwt = st[o8 + 0 * (size_t)n];
-  s.wa = st[o8 + 1 * (size_t)n];
-  s.LAI = st[o8 + 2 * (size_t)n];
-  s.LAI_litter = st[o8 + 3 * (size_t)n];
-  s.pm = st[o8 + 4 * (size_t)n];
-  s.pfm = st[o8 + 5 * (size_t)n];
-  s.plen = st[o8 + 6 * (size_t)n];
-  s.rdepth = st[o8 + 7 * (size_t)n];
+  H9K_LOAD_SCALARS(L, s, st, n, c)
   cs.launder();
 
   if (!spare) {
-    // soil mask (HYBRID9.f90:122-123): SUM(theta_s) > trunc
-    float ts_sum = zero;
-#pragma unroll
-    for (int i = 1; i <= L; i++) ts_sum = ts_sum + cs.lay(PF_TS, i);
-    if (!(ts_sum > 1.0E-8f) || err[c] != 0) {
-      if (h == 0)
-#pragma unroll
-        for (int r = 0; r < 12 + L; r++) a.annual[(size_t)r * ios + io] = __builtin_nanf("");
+    H9K_TS_SUM(L, cs, ts_sum)
+    if (!(ts_sum > SOIL_TRUNC) || err[c] != 0) {
+      if (h == 0) nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
       return;
     }
     cell_inv_pair<L, G>(g, cs);
@@ -247,30 +237,10 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g) {
   opaque(iow);
   cs.launder();
   if (hist) hist[cw] = s.naq;
-  const size_t ow = (size_t)(4 * L + 1) * n + cw;
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    st[(size_t)(0 * L + i - 1) * n + cw] = s.h2o[i];
-    st[(size_t)(2 * L + i - 1) * n + cw] = s.smp[i];
-    if (a.grow_on) st[(size_t)(3 * L + i - 1) * n + cw] = cs.lay(PF_ROOTR, i);
-  }
-  if (a.grow_on) st[(size_t)(4 * L) * n + cw] = zero;   // rootr_col(Nlevgrnd)
-  st[ow + 0 * (size_t)n] = s.zwt;
-  st[ow + 1 * (size_t)n] = s.wa;
-  st[ow + 2 * (size_t)n] = s.LAI;
-  st[ow + 3 * (size_t)n] = s.LAI_litter;
-  st[ow + 4 * (size_t)n] = s.pm;
-  st[ow + 5 * (size_t)n] = s.pfm;
-  st[ow + 6 * (size_t)n] = s.plen;
-  st[ow + 7 * (size_t)n] = s.rdepth;
+  H9K_STORE_CELL(L, s, cs, st, n, cw, a.grow_on, SC_N)
   if (code) {
-    err[0 * (size_t)n + cw] = code;
-    err[1 * (size_t)n + cw] = eday;
-    err[2 * (size_t)n + cw] = estep;
-    err[3 * (size_t)n + cw] = __builtin_bit_cast(int, errval);
-    atomicOr(a.err_flag, 1);
-#pragma unroll
-    for (int r = 0; r < 12 + L; r++) a.annual[(size_t)r * ios + iow] = __builtin_nanf("");
+    stop_write(err, n, cw, code, eday, estep, errval, a.err_flag);
+    nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);
   }
 }
 
@@ -345,33 +315,12 @@ h9g_solo_kernel(const KArgs a, const G g) {
   SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};
   const SplitAll sp;
   St<L> s;
-#pragma unroll
-  for (int p = 0; p < 4; p++)
-#pragma unroll
-    for (int i = 1; i <= L; i++) cs.set_lay(p, i, a.par[(size_t)(p * L + i - 1) * n + c]);
-  cs.set_sc(PS_FMAX, a.par[(size_t)(4 * L) * n + c]);
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    s.h2o[i] = a.st[(size_t)(0 * L + i - 1) * n + c];
-    s.smp[i] = a.st[(size_t)(2 * L + i - 1) * n + c];
-    cs.set_lay(PF_ROOTR, i, a.st[(size_t)(3 * L + i - 1) * n + c]);
-  }
-  const size_t o8 = (size_t)(4 * L + 1) * n + c;
-  s.zwt = a.st[o8 + 0 * (size_t)n];
-  s.wa = a.st[o8 + 1 * (size_t)n];
-  s.LAI = a.st[o8 + 2 * (size_t)n];
-  s.LAI_litter = a.st[o8 + 3 * (size_t)n];
-  s.pm = a.st[o8 + 4 * (size_t)n];
-  s.pfm = a.st[o8 + 5 * (size_t)n];
-  s.plen = a.st[o8 + 6 * (size_t)n];
-  s.rdepth = a.st[o8 + 7 * (size_t)n];
+  H9K_LOAD_LANE(L, cs, s, a.par, n, c, a.st, n, c)
+  H9K_LOAD_SCALARS(L, s, a.st, n, c)
   cs.launder();
-  float ts_sum = zero;
-#pragma unroll
-  for (int i = 1; i <= L; i++) ts_sum = ts_sum + cs.lay(PF_TS, i);
-  if (!(ts_sum > 1.0E-8f) || a.err[c] != 0) {
-#pragma unroll
-    for (int r = 0; r < 12 + L; r++) a.annual[(size_t)r * ios + io] = __builtin_nanf("");
+  H9K_TS_SUM(L, cs, ts_sum)
+  if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {
+    nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
     return;
   }
   cell_inv_pair<L, G>(g, cs);
@@ -385,30 +334,10 @@ h9g_solo_kernel(const KArgs a, const G g) {
   opaque(iow);
   cs.launder();
   if (a.hist) a.hist[cw] = s.naq;
-  const size_t ow = (size_t)(4 * L + 1) * n + cw;
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    a.st[(size_t)(0 * L + i - 1) * n + cw] = s.h2o[i];
-    a.st[(size_t)(2 * L + i - 1) * n + cw] = s.smp[i];
-    if (a.grow_on) a.st[(size_t)(3 * L + i - 1) * n + cw] = cs.lay(PF_ROOTR, i);
-  }
-  if (a.grow_on) a.st[(size_t)(4 * L) * n + cw] = zero;
-  a.st[ow + 0 * (size_t)n] = s.zwt;
-  a.st[ow + 1 * (size_t)n] = s.wa;
-  a.st[ow + 2 * (size_t)n] = s.LAI;
-  a.st[ow + 3 * (size_t)n] = s.LAI_litter;
-  a.st[ow + 4 * (size_t)n] = s.pm;
-  a.st[ow + 5 * (size_t)n] = s.pfm;
-  a.st[ow + 6 * (size_t)n] = s.plen;
-  a.st[ow + 7 * (size_t)n] = s.rdepth;
+  H9K_STORE_CELL(L, s, cs, a.st, n, cw, a.grow_on, SC_N)
   if (code) {
-    a.err[0 * (size_t)n + cw] = code;
-    a.err[1 * (size_t)n + cw] = eday;
-    a.err[2 * (size_t)n + cw] = estep;
-    a.err[3 * (size_t)n + cw] = __builtin_bit_cast(int, errval);
-    atomicOr(a.err_flag, 1);
-#pragma unroll
-    for (int r = 0; r < 12 + L; r++) a.annual[(size_t)r * ios + iow] = __builtin_nanf("");
+    stop_write(a.err, n, cw, code, eday, estep, errval, a.err_flag);
+    nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);
   }
 }
 
@@ -483,7 +412,8 @@ __global__ void __launch_bounds__(256) h9g_chain_kernel(int m, int n, int L, con
   const int p = pred[j];
   int differ = 0;
   for (int i = 0; i < L; i++) {
-    const float v = src[(size_t)(2 * L + i) * n + p];
+    // (smp_row(L, 0) + i, here and below: as smp_row(L, i), chain_start and restart take two more SGPRs)
+    const float v = src[(size_t)(smp_row(L, 0) + i) * n + p];
     differ |= __float_as_uint(v) != __float_as_uint(guess[(size_t)i * n + k]);
     guess[(size_t)i * n + k] = v;
   }
@@ -509,11 +439,9 @@ __global__ void __launch_bounds__(256) h9g_probe_cmp_kernel(int m, int n, int sr
   if (j >= m) return;
   const int c = list[j];
   bool same = true;
-  for (int r = 0; r < srows; r++)
-    same &= __float_as_uint(stA[(size_t)r * n + c]) == __float_as_uint(stB[(size_t)r * n + c]);
-  for (int r = 0; r < 4; r++) same &= errA[(size_t)r * n + c] == errB[(size_t)r * n + c];
-  for (int r = 0; r < rows; r++)
-    same &= __float_as_uint(annA[(size_t)r * n + c]) == __float_as_uint(annB[(size_t)r * n + c]);
+  H9K_SAME_CELL(same, stA, stB, n, c, srows);
+  H9K_SAME_CELL(same, errA, errB, n, c, STOP_ROWS);
+  H9K_SAME_CELL(same, annA, annB, n, c, rows);
   keep[j] = !same;
 }
 
@@ -533,19 +461,18 @@ __global__ void __launch_bounds__(256) h9g_settle_kernel(int n, int srows, int r
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
   bool same = true;
-  for (int r = 0; r < srows; r++)
-    same &= __float_as_uint(fin[(size_t)r * n + c]) == __float_as_uint(st0[(size_t)r * n + c]);
-  for (int r = 0; r < 4; r++) same &= fin_err[(size_t)r * n + c] == err0[(size_t)r * n + c];
+  H9K_SAME_CELL(same, fin, st0, n, c, srows);
+  H9K_SAME_CELL(same, fin_err, err0, n, c, STOP_ROWS);
   if (same) return;
-  for (int r = 0; r < srows; r++) st0[(size_t)r * n + c] = fin[(size_t)r * n + c];
-  for (int r = 0; r < 4; r++) err0[(size_t)r * n + c] = fin_err[(size_t)r * n + c];
+  H9K_COPY_CELL(st0, n, c, fin, n, c, srows);
+  H9K_COPY_CELL(err0, n, c, fin_err, n, c, STOP_ROWS);
   dirty[c] = 1;
   if (err0[c] == 0) return;
   for (int r = 0; r < srows; r++) {
     st[(size_t)r * n + c] = st0[(size_t)r * n + c];
     ck_last[(size_t)r * n + c] = st0[(size_t)r * n + c];
   }
-  for (int r = 0; r < 4; r++) {
+  for (int r = 0; r < STOP_ROWS; r++) {
     err[(size_t)r * n + c] = err0[(size_t)r * n + c];
     eck_last[(size_t)r * n + c] = err0[(size_t)r * n + c];
   }
@@ -563,8 +490,8 @@ __global__ void __launch_bounds__(256) h9g_chain_start_kernel(int m, int n, int 
   if (j >= m || !first[j]) return;
   const int k = chain[j], p = pred[j];
   for (int i = 0; i < L; i++) {
-    const float v = st0[(size_t)(2 * L + i) * n + p];
-    st[(size_t)(2 * L + i) * n + k] = v;
+    const float v = st0[(size_t)(smp_row(L, 0) + i) * n + p];
+    st[(size_t)(smp_row(L, 0) + i) * n + k] = v;
     guess[(size_t)i * n + k] = v;
   }
 }
@@ -578,10 +505,10 @@ __global__ void __launch_bounds__(256) h9g_restart_kernel(int m, int n, int L, c
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
   const int k = list[j];
-  const int rows = 4 * L + 9;
-  for (int r = 0; r < rows; r++) st[(size_t)r * n + k] = st0[(size_t)r * n + k];
-  for (int i = 0; i < L; i++) st[(size_t)(2 * L + i) * n + k] = guess[(size_t)i * n + k];
-  for (int r = 0; r < 4; r++) err[(size_t)r * n + k] = err0[(size_t)r * n + k];
+  const int rows = state_rows(L);
+  H9K_COPY_CELL(st, n, k, st0, n, k, rows);
+  for (int i = 0; i < L; i++) st[(size_t)(smp_row(L, 0) + i) * n + k] = guess[(size_t)i * n + k];
+  H9K_COPY_CELL(err, n, k, err0, n, k, STOP_ROWS);
 }
 
 // A re-run cell's trajectory against the one its last run took (ckpt: the
@@ -601,15 +528,14 @@ __global__ void __launch_bounds__(256) h9g_merge_kernel(int m, int n, int rows, 
   if (j >= m) return;
   const int k = list[j];
   bool same = true;
-  for (int r = 0; r < rows; r++)
-    same &= __float_as_uint(st[(size_t)r * n + k]) == __float_as_uint(ckpt[(size_t)r * n + k]);
-  for (int r = 0; r < 4; r++) same &= err[(size_t)r * n + k] == eckpt[(size_t)r * n + k];
+  H9K_SAME_CELL(same, st, ckpt, n, k, rows);
+  H9K_SAME_CELL(same, err, eckpt, n, k, STOP_ROWS);
   if (same) {
-    for (int r = 0; r < rows; r++) st[(size_t)r * n + k] = ckpt_last[(size_t)r * n + k];
-    for (int r = 0; r < 4; r++) err[(size_t)r * n + k] = eckpt_last[(size_t)r * n + k];
+    H9K_COPY_CELL(st, n, k, ckpt_last, n, k, rows);
+    H9K_COPY_CELL(err, n, k, eckpt_last, n, k, STOP_ROWS);
   } else {
-    for (int r = 0; r < rows; r++) ckpt[(size_t)r * n + k] = st[(size_t)r * n + k];
-    for (int r = 0; r < 4; r++) eckpt[(size_t)r * n + k] = err[(size_t)r * n + k];
+    H9K_COPY_CELL(ckpt, n, k, st, n, k, rows);
+    H9K_COPY_CELL(eckpt, n, k, err, n, k, STOP_ROWS);
   }
   keep[j] = !same;
 }
@@ -657,7 +583,7 @@ __global__ void __launch_bounds__(H9G_SORT_THREADS)
   float zim[L + 1];
 #pragma unroll
   for (int i = 1; i <= L; i++) zim[i] = g.zim(i);
-  const float *zwt = st + (size_t)(4 * L + 1) * n;
+  const float *zwt = st + (size_t)scalar_row(L, SC_ZWT) * n;
   auto key = [&](int c) -> int {
     if (err[c]) return L + 9;
     const int j = jwt_of<L>(zwt[c], zim);
@@ -737,33 +663,12 @@ __global__ void __launch_bounds__(64) h9g_site_kernel(const SiteArgs a, const G 
   const int n = a.ncell;
   SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};
   St<L> s;
-#pragma unroll
-  for (int p = 0; p < 4; p++)
-#pragma unroll
-    for (int i = 1; i <= L; i++) cs.set_lay(p, i, a.par[(size_t)(p * L + i - 1) * n + c]);
-  cs.set_sc(PS_FMAX, a.par[(size_t)(4 * L) * n + c]);
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    s.h2o[i] = a.st[(size_t)(0 * L + i - 1) * n + c];
-    s.smp[i] = a.st[(size_t)(2 * L + i - 1) * n + c];
-    cs.set_lay(PF_ROOTR, i, a.st[(size_t)(3 * L + i - 1) * n + c]);
-  }
-  const float h2o_ma1 = a.st[(size_t)(1 * L) * n + c];
-  const size_t o8 = (size_t)(4 * L + 1) * n + c;
-  s.zwt = a.st[o8 + 0 * (size_t)n];
-  s.wa = a.st[o8 + 1 * (size_t)n];
-  s.LAI = a.st[o8 + 2 * (size_t)n];
-  s.LAI_litter = a.st[o8 + 3 * (size_t)n];
-  s.pm = a.st[o8 + 4 * (size_t)n];
-  s.pfm = a.st[o8 + 5 * (size_t)n];
-  s.plen = a.st[o8 + 6 * (size_t)n];
-  s.rdepth = a.st[o8 + 7 * (size_t)n];
-  float ts_sum = zero;
-#pragma unroll
-  for (int i = 1; i <= L; i++) ts_sum = ts_sum + cs.lay(PF_TS, i);
-  if (!(ts_sum > 1.0E-8f) || a.err[c] != 0) {
-    for (int d = 0; d < a.nday; d++)
-      for (int r = 0; r < 11; r++) a.out[((size_t)d * 11 + r) * n + c] = __builtin_nanf("");
+  H9K_LOAD_LANE(L, cs, s, a.par, n, c, a.st, n, c)
+  const float h2o_ma1 = a.st[(size_t)Rows<L>::H2O_MA * n + c];
+  H9K_LOAD_SCALARS(L, s, a.st, n, c)
+  H9K_TS_SUM(L, cs, ts_sum)
+  if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {
+    for (int d = 0; d < a.nday; d++) nan_rows(a.out + (size_t)d * DAILY_ROWS * n, DAILY_ROWS, n, c);
     return;
   }
   cell_inv_pair<L, G>(g, cs);
@@ -771,24 +676,10 @@ __global__ void __launch_bounds__(64) h9g_site_kernel(const SiteArgs a, const G 
   float errval = 0.0f;
   const int code = cell_site<L, G, SS>(g, cs, s, h2o_ma1, a.sub + c, a.daily + c, a.lai + c, a.out + c,
                                        (size_t)n, a.nday, a.nisurf, eday, estep, errval, T);
-  const size_t ow = (size_t)(4 * L + 1) * n + c;
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    a.st[(size_t)(0 * L + i - 1) * n + c] = s.h2o[i];
-    a.st[(size_t)(2 * L + i - 1) * n + c] = s.smp[i];
-  }
-  a.st[ow + 0 * (size_t)n] = s.zwt;
-  a.st[ow + 1 * (size_t)n] = s.wa;
-  a.st[ow + 2 * (size_t)n] = s.LAI;
-  a.st[ow + 3 * (size_t)n] = s.LAI_litter;
+  H9K_STORE_CELL(L, s, cs, a.st, n, c, false, SC_SITE)
   if (code) {
-    a.err[0 * (size_t)n + c] = code;
-    a.err[1 * (size_t)n + c] = eday;
-    a.err[2 * (size_t)n + c] = estep;
-    a.err[3 * (size_t)n + c] = __builtin_bit_cast(int, errval);
-    atomicOr(a.err_flag, 1);
-    for (int d = eday; d < a.nday; d++)
-      for (int r = 0; r < 11; r++) a.out[((size_t)d * 11 + r) * n + c] = __builtin_nanf("");
+    stop_write(a.err, n, c, code, eday, estep, errval, a.err_flag);
+    for (int d = eday; d < a.nday; d++) nan_rows(a.out + (size_t)d * DAILY_ROWS * n, DAILY_ROWS, n, c);
   }
 }
 
@@ -820,9 +711,9 @@ __global__ void __launch_bounds__(256) h9g_focus_gather_kernel(int nsel, int n, 
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nsel) return;
   const int c = sel[j];
-  for (int r = 0; r < srows; r++) dst[(size_t)r * nsel + j] = st[(size_t)r * n + c];
+  H9K_COPY_CELL(dst, nsel, j, st, n, c, srows);
   if (guess)
-    for (int i = 0; i < L; i++) dst[(size_t)(2 * L + i) * nsel + j] = guess[(size_t)i * n + c];
+    for (int i = 0; i < L; i++) dst[(size_t)(smp_row(L, 0) + i) * nsel + j] = guess[(size_t)i * n + c];
 }
 
 template <int L, class G>
@@ -841,42 +732,27 @@ __global__ void __launch_bounds__(64) h9g_focus_kernel(const FocusArgs a, const 
   const int n = a.ncell, m = a.nsel;
   SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};
   St<L> s;
-#pragma unroll
-  for (int p = 0; p < 4; p++)
-#pragma unroll
-    for (int i = 1; i <= L; i++) cs.set_lay(p, i, a.par[(size_t)(p * L + i - 1) * n + c]);
-  cs.set_sc(PS_FMAX, a.par[(size_t)(4 * L) * n + c]);
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    s.h2o[i] = a.st[(size_t)(0 * L + i - 1) * m + j];
-    s.smp[i] = a.st[(size_t)(2 * L + i - 1) * m + j];
-    cs.set_lay(PF_ROOTR, i, a.st[(size_t)(3 * L + i - 1) * m + j]);
-  }
-  const float h2o_ma1 = a.st[(size_t)(1 * L) * m + j];
-  const size_t o8 = (size_t)(4 * L + 1) * m + j;
-  s.zwt = a.st[o8 + 0 * (size_t)m];
-  s.wa = a.st[o8 + 1 * (size_t)m];
-  s.LAI = a.st[o8 + 2 * (size_t)m];
-  s.LAI_litter = a.st[o8 + 3 * (size_t)m];
-  s.pm = a.st[o8 + 4 * (size_t)m];
-  s.pfm = a.st[o8 + 5 * (size_t)m];
-  s.plen = a.st[o8 + 6 * (size_t)m];
-  s.rdepth = a.st[o8 + 7 * (size_t)m];
+  H9K_LOAD_LANE(L, cs, s, a.par, n, c, a.st, m, j)
+  const float h2o_ma1 = a.st[(size_t)Rows<L>::H2O_MA * m + j];
+  H9K_LOAD_SCALARS(L, s, a.st, m, j)
   s.naq = 0;
-  float ts_sum = zero;
-#pragma unroll
-  for (int i = 1; i <= L; i++) ts_sum = ts_sum + cs.lay(PF_TS, i);
-  if (!(ts_sum > 1.0E-8f) || a.err[c] != 0) {      // masked, or stopped before the run: no line at all
+  H9K_TS_SUM(L, cs, ts_sum)
+  if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {      // masked, or stopped before the run: no line at all
     size_t d = 0;
     for (int y = 0; y < a.nyears; y++)
-      for (int k = 0; k < a.yrs[y].nt; k++, d++)
-        for (int r = 0; r < 11; r++) a.out[(d * 11 + r) * m + j] = __builtin_nanf("");
+      for (int k = 0; k < a.yrs[y].nt; k++, d++) nan_rows(a.out + d * DAILY_ROWS * m, DAILY_ROWS, m, j);
     return;
   }
   cell_inv_pair<L, G>(g, cs);
   cell_focus<L, G, SS>(g, cs, s, h2o_ma1, a.yrs, a.nyears, (size_t)c, (size_t)n, a.fvar, a.nisurf, a.grow_on,
                        a.out + j, (size_t)m, T);
 }
+
+// init_cell's rootr array as H9K_STORE_CELL reads a store's rootr rows
+struct InitRoots {
+  const float *r;
+  __device__ __forceinline__ float lay(int, int i) const { return r[i]; }
+};
 
 template <int L, class G>
 __global__ void __launch_bounds__(H9G_BLOCK) h9g_init_kernel(int ncell, const float *__restrict__ par,
@@ -892,25 +768,12 @@ __global__ void __launch_bounds__(H9G_BLOCK) h9g_init_kernel(int ncell, const fl
   St<L> s;
   float h2o_ma[L + 1], rootr[L + 1];
 #pragma unroll
-  for (int i = 1; i <= L; i++) ts[i] = par[(size_t)(i - 1) * n + c];
+  for (int i = 1; i <= L; i++) ts[i] = par[(size_t)par_row(L, PF_TS, i - 1) * n + c];
   init_cell<L, G, MathExact>(g, ts, s, rootr, h2o_ma, me);
+  const InitRoots roots{rootr};
+  H9K_STORE_CELL(L, s, roots, st, n, c, true, SC_N)
 #pragma unroll
-  for (int i = 1; i <= L; i++) {
-    st[(size_t)(0 * L + i - 1) * n + c] = s.h2o[i];
-    st[(size_t)(1 * L + i - 1) * n + c] = h2o_ma[i];
-    st[(size_t)(2 * L + i - 1) * n + c] = s.smp[i];
-    st[(size_t)(3 * L + i - 1) * n + c] = rootr[i];
-  }
-  st[(size_t)(4 * L) * n + c] = zero;
-  const size_t o8 = (size_t)(4 * L + 1) * n + c;
-  st[o8 + 0 * (size_t)n] = s.zwt;
-  st[o8 + 1 * (size_t)n] = s.wa;
-  st[o8 + 2 * (size_t)n] = s.LAI;
-  st[o8 + 3 * (size_t)n] = s.LAI_litter;
-  st[o8 + 4 * (size_t)n] = s.pm;
-  st[o8 + 5 * (size_t)n] = s.pfm;
-  st[o8 + 6 * (size_t)n] = s.plen;
-  st[o8 + 7 * (size_t)n] = s.rdepth;
+  for (int i = 1; i <= L; i++) st[(size_t)(Rows<L>::H2O_MA + i - 1) * n + c] = h2o_ma[i];
 }
 
 // deterministic FP64 diagnostics: one block, fixed strided order + tree
@@ -921,7 +784,7 @@ __global__ void __launch_bounds__(1024) h9g_diag_kernel(int ncell, int L, const 
   double acc[H9G_NDIAG];
   for (int k = 0; k < H9G_NDIAG; k++) acc[k] = 0.0;
   const size_t n = ncell;
-  const size_t o8 = (size_t)(4 * L + 1) * n;
+  const size_t o8 = (size_t)scalar_row(L, 0) * n;
   for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
     const float rnf = annual[2 * n + c];
     if (err[c] != 0) { acc[11] += 1.0; continue; }
@@ -929,11 +792,11 @@ __global__ void __launch_bounds__(1024) h9g_diag_kernel(int ncell, int L, const 
     acc[0] += 1.0;
     acc[1] += (double)rnf;
     acc[2] += (double)annual[(size_t)(11 + L) * n + c];
-    acc[3] += (double)st[o8 + 0 * n + c];
-    acc[4] += (double)st[o8 + 1 * n + c];
+    acc[3] += (double)st[o8 + SC_ZWT * n + c];
+    acc[4] += (double)st[o8 + SC_WA * n + c];
     acc[5] += (double)annual[0 * n + c];
     acc[6] += (double)annual[1 * n + c];
-    acc[7] += (double)st[o8 + 2 * n + c];
+    acc[7] += (double)st[o8 + SC_LAI * n + c];
     acc[8] += (double)annual[11 * n + c];
     acc[9] += (double)annual[4 * n + c];
     acc[10] += (double)annual[9 * n + c];
@@ -961,12 +824,12 @@ __global__ void __launch_bounds__(H9G_BLOCK) h9g_synth_params_kernel(int ncell, 
   for (int l = 0; l < L; l++) {
     float ts, hk, b, ps;
     h9s::params(seed, g, l, &ts, &hk, &b, &ps);
-    par[(size_t)(0 * L + l) * n + c] = ts;
-    par[(size_t)(1 * L + l) * n + c] = hk;
-    par[(size_t)(2 * L + l) * n + c] = b;
-    par[(size_t)(3 * L + l) * n + c] = ps;
+    par[(size_t)par_row(L, PF_TS, l) * n + c] = ts;
+    par[(size_t)par_row(L, PF_HKS, l) * n + c] = hk;
+    par[(size_t)par_row(L, PF_BSW, l) * n + c] = b;
+    par[(size_t)par_row(L, PF_PSI, l) * n + c] = ps;
   }
-  par[(size_t)(4 * L) * n + c] = h9s::fmax_param(seed, g);
+  par[(size_t)fmax_row(L) * n + c] = h9s::fmax_param(seed, g);
 }
 
 __global__ void __launch_bounds__(H9G_BLOCK) h9g_synth_forcing_kernel(int ncell, int nday, int day0,
@@ -1004,7 +867,7 @@ struct SoilOut {
     else if (v == 1) out = 10.0f * m / 86400.0f;                  // hksat        :614
     else if (v == 2) out = 1.0f / MAXF(m / 1.0E3f, 1.0E-8f);      // bsw          :615,624,628
     else out = 10.0f * m;                                         // psi_s        :616
-    par[(size_t)(v * L + layer) * n + c] = out;
+    par[(size_t)par_row(L, v, layer) * n + c] = out;
   }
 };
 
@@ -1148,6 +1011,40 @@ __global__ void h9g_math_fast_kernel(int n, const float *x, const float *y, floa
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// Kernel kinds: what a context runs its years on (h9g_ctx::kind, H9G_KERNEL)
+// and what a launch ran on (the rows of h9g_launch_stats, which the Python
+// layer names: the numbers stay).
+enum Kind : int {
+  K_PAIR = 1,     // h9g_pair_kernel
+  K_SOLO = 2,     // h9g_solo_kernel
+  K_MIXED = 3,    // whole rounds of solo waves, then the pair kernel on the rest (l10_kind)
+  K_PAIR2 = 4,    // h9g_pair2_kernel (L = 10)
+  K_PAIR11 = 5,   // h9g_pair11_kernel
+  K_PAIR1 = 6,    // h9g_pair1_kernel
+  K_PROBE = 7,    // statistics only: the cell order's day-1 probes, whatever kernel ran them
+  K_NSTAT         // rows of h9g_ctx::kstat
+};
+struct KindInfo {
+  const char *env;      // H9G_KERNEL value
+  int wave_cols;        // columns per wave (of its pair part)
+  int resident;         // workgroups resident per CU = waves per SIMD (the Pacer's round, pace_mode)
+  bool pair;            // launches a pair kernel (day-snapshot blocks, pacing rows)
+  bool second_group;    // its launches can carry a second group of cells (g2_fits)
+  Kind pair_part;       // the kind its pair part, and a list launch of its context, runs as
+  int block_cells;      // cells per workgroup (of its pair part)
+};
+static constexpr KindInfo kind_info(int kind) {
+  switch (kind) {
+    // (the solo kernel does not pace: its `resident` only fills KArgs::prio_mode as the pair kernel's would)
+    case K_SOLO: return {"solo", H9G_YBLOCK, pair_resident<8>(), false, false, K_SOLO, H9G_YBLOCK};
+    case K_MIXED: return {"mixed", H9G_PCPW, pair_resident<8>(), true, false, K_PAIR, H9G_PCPW * H9G_PWAVES};
+    case K_PAIR2: return {"pair2", H9G_PCPW, 2, true, true, K_PAIR2, H9G_PCPW * H9G_PWAVES};
+    case K_PAIR11: return {"pair11", H9G_PCPW11, pair_resident<8>(), true, true, K_PAIR11, H9G_PCPW11 * H9G_PWAVES};
+    case K_PAIR1: return {"pair1", 1, 1, true, false, K_PAIR1, H9G_PWAVES};
+    default: return {"pair", H9G_PCPW, pair_resident<8>(), true, true, K_PAIR, H9G_PCPW * H9G_PWAVES};
+  }
+}
+
 struct h9g_ctx {
   h9g_config cfg;
   int device = 0;
@@ -1169,7 +1066,7 @@ struct h9g_ctx {
   int last_year = 0;
   int params_set = 0, state_set = 0, ran = 0;
   h9g_error last_err{};
-  const char *kname = "";
+  std::string kname;
   unsigned *d_stamps = nullptr;   // H9G_STAMPS builds only
   std::vector<int64_t> h_gid;     // grid ids of the cells (h9g_set_cells), for NetCDF ingest
   std::vector<float *> h_pin;     // per-slot pinned staging of the NetCDF prefetch
@@ -1196,15 +1093,13 @@ struct h9g_ctx {
   int ncu = 256;
   int sort = 1;                   // H9G_SORT=0: identity order
   size_t sv_bytes = 0;
-  int kind = 1;        // 1: h9g_pair_kernel, 2: h9g_solo_kernel, 3: both, 4: h9g_pair2_kernel (L = 10),
-                       // 5: h9g_pair11_kernel, 6: h9g_pair1_kernel (H9G_KERNEL=pair|solo|mixed|pair2|pair11|
-                       // pair1; default by L and the shard size, l10_kind)
-  size_t n_solo = 0;   // kind 3: cells [0, n_solo) run on the solo kernel, the rest on the pair kernel
+  Kind kind = K_PAIR;  // H9G_KERNEL=pair|solo|mixed|pair2|pair11|pair1; default by L and the shard size, l10_kind
+  size_t n_solo = 0;   // K_MIXED: cells [0, n_solo) run on the solo kernel, the rest on the pair kernel
   size_t ios = 0;      // slots of the slot-ordered buffers (d_perm, d_forc_s, d_ann_s): twice the cells
   size_t stamp_words = 0;
   int ev_kind[NEVT] = {};         // kernel kind and cell-years of each timed launch
   int64_t ev_cells[NEVT] = {};
-  double kstat[8][3] = {};        // per kernel kind: launches, cell-years, ms (h9g_launch_stats)
+  double kstat[K_NSTAT][3] = {};        // per kernel kind: launches, cell-years, ms (h9g_launch_stats)
   struct OrdBufs *ord = nullptr;  // h9g_run_ordered's decade buffers
   int64_t ord_stats[9] = {};      // last ordered call (h9g_ordered_stats)
   int ord_probe = 1;              // the checks' day-1 probe (H9G_NO_PROBE: off)
@@ -1334,7 +1229,7 @@ int h9g_device_count(void) {
   return n;
 }
 
-int h9g_state_size(int nlayers) { return 4 * nlayers + 9; }
+int h9g_state_size(int nlayers) { return state_rows(nlayers); }
 
 void h9g_destroy(h9g_ctx *ctx) {
   if (!ctx) return;
@@ -1381,11 +1276,11 @@ void h9g_destroy(h9g_ctx *ctx) {
   delete ctx;
 }
 
-// Kernel for L = 10 (1: pair, 2: solo, 3: both).  They are bit-identical
+// Kernel for L = 10 (pair, solo or both).  They are bit-identical
 // and differ in how n columns quantise into rounds of resident waves: the
 // solo kernel (1-wave blocks, 1 wave/SIMD) packs 64 columns per wave, the
 // pair kernel (88-column blocks, 3 waves/SIMD since round 3, pair_resident)
-// 22; kind 3 runs the whole solo rounds and the pair kernel on the rest.
+// 22; K_MIXED runs the whole solo rounds and the pair kernel on the rest.
 // Round 3 measured every strong-scaling shard of the config-5 grid
 // (tools/l10_shards.py, profiles/r03e_l10_shards.txt, ms per year, pair /
 // solo / mixed): 270,000 cells 537.7 / 618.6 / 538.1; 135,000 274.5 / 373.2 /
@@ -1393,17 +1288,17 @@ void h9g_destroy(h9g_ctx *ctx) {
 // pair kernel is within noise of the best everywhere, so it is the choice;
 // round 2's rounds model picked solo at 33,750 cells (24% slower there).
 // Solo and mixed stay selectable (H9G_KERNEL) and are tested.  *n_solo:
-// the whole solo rounds (kind 3 only).
-// Round 4 adds the pair kernel built for 2 waves per SIMD (kind 4, 256
+// the whole solo rounds (K_MIXED only).
+// Round 4 adds the pair kernel built for 2 waves per SIMD (K_PAIR2, 256
 // VGPRs: no spills, every reciprocal): where the shard's pair workgroups fit
 // one round of 2 per CU it is the faster one (33,750 cells: 98.1 vs 100.9 ms
 // per year), and wherever they do not it needs an extra round (270,000 cells:
 // 601.5 vs 505.8 ms), profiles/r04*_l10_shards.txt.
-static int l10_kind(size_t n, int ncu, size_t *n_solo) {
+static Kind l10_kind(size_t n, int ncu, size_t *n_solo) {
   const size_t solo_round = (size_t)4 * ncu * H9G_YBLOCK;
   *n_solo = (n / solo_round) * solo_round;
   const size_t blocks = (n + (size_t)H9G_PCPW * H9G_PWAVES - 1) / ((size_t)H9G_PCPW * H9G_PWAVES);
-  return blocks <= (size_t)2 * ncu ? 4 : 1;
+  return blocks <= (size_t)kind_info(K_PAIR2).resident * ncu ? K_PAIR2 : K_PAIR;
 }
 
 // Device bytes a context of this configuration allocates: h9g_create's
@@ -1417,12 +1312,12 @@ static int l10_kind(size_t n, int ncu, size_t *n_solo) {
 // Device bytes of the ordered mode's buffers for decades of up to ny years
 // (h9g_config_bytes counts them with ny = 10).
 static size_t ord_bytes(size_t n, size_t L, size_t ny) {
-  const size_t srows = 4 * L + 9, rows = 12 + L;
-  return 2 * (sizeof(float) * (srows + L + ny * (rows + srows)) * n + sizeof(int) * (4 + 4 * ny + 1) * n +
+  const size_t srows = state_rows((int)L), rows = annual_rows((int)L);
+  return 2 * (sizeof(float) * (srows + L + ny * (rows + srows)) * n + sizeof(int) * (STOP_ROWS + STOP_ROWS * ny + 1) * n +
               sizeof(int) * 5 * (n + 1)) +
-         sizeof(float) * srows * n + sizeof(int) * (4 * n + n + 1) +
+         sizeof(float) * srows * n + sizeof(int) * (STOP_ROWS * n + n + 1) +
          // the day-1 probe (OrdBufs): old inputs, two runs' state, sums and STOP rows, list, flags
-         sizeof(float) * (L + 2 * srows + 2 * rows) * n + sizeof(int) * (8 * n + 2 * (n + 1));
+         sizeof(float) * (L + 2 * srows + 2 * rows) * n + sizeof(int) * (2 * STOP_ROWS * n + 2 * (n + 1));
 }
 
 size_t h9g_config_bytes(const h9g_config *cfg) {
@@ -1436,9 +1331,10 @@ size_t h9g_config_bytes(const h9g_config *cfg) {
   // + the slot-ordered copies of a forcing slot and of the annual sums
   // (h9g_run_year, allocated on first use), the ordered mode's decade
   // buffers (h9g_run_ordered, decades of up to 10 years)
-  return sizeof(float) * ((4 * L + 1) + (4 * L + 9) + 7 * (size_t)cfg->max_days * (size_t)cfg->nslots + (12 + L) + 1) * n +
-         sizeof(float) * (7 * (size_t)cfg->max_days + 12 + L) * ios + sizeof(int) * 2 * ios +
-         sizeof(int) * 6 * n + sizeof(int64_t) * n + sizeof(double) * H9G_NDIAG + sizeof(int) +
+  const size_t prows = par_rows(cfg->nlayers), srows = state_rows(cfg->nlayers), arows = annual_rows(cfg->nlayers);
+  return sizeof(float) * (prows + srows + 7 * (size_t)cfg->max_days * (size_t)cfg->nslots + arows + 1) * n +
+         sizeof(float) * (7 * (size_t)cfg->max_days + arows) * ios + sizeof(int) * 2 * ios +
+         sizeof(int) * (STOP_ROWS + 2) * n + sizeof(int64_t) * n + sizeof(double) * H9G_NDIAG + sizeof(int) +
          blocks * PairStore<8, H9G_PLANES>::GBLOCK + sizeof(unsigned) * 16 * (size_t)H9G_PACE_ROWS +
          ord_bytes(n, L, 10);
 }
@@ -1504,11 +1400,11 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
   ctx->ios = 2 * round_up(n, H9G_PCPW) + 64;
   bool ok = hipStreamCreateWithFlags(&ctx->sc, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&ctx->sx, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&ctx->d_par, sizeof(float) * (4 * L + 1) * n) == hipSuccess &&
-            hipMalloc(&ctx->d_st, sizeof(float) * (4 * L + 9) * n) == hipSuccess &&
+            hipMalloc(&ctx->d_par, sizeof(float) * par_rows(L) * n) == hipSuccess &&
+            hipMalloc(&ctx->d_st, sizeof(float) * state_rows(L) * n) == hipSuccess &&
             hipMalloc(&ctx->d_forc, sizeof(float) * 7 * (size_t)cfg->max_days * n * cfg->nslots) == hipSuccess &&
-            hipMalloc(&ctx->d_ann, sizeof(float) * (12 + L) * n) == hipSuccess &&
-            hipMalloc(&ctx->d_err, sizeof(int) * 4 * n) == hipSuccess &&
+            hipMalloc(&ctx->d_ann, sizeof(float) * annual_rows(L) * n) == hipSuccess &&
+            hipMalloc(&ctx->d_err, sizeof(int) * STOP_ROWS * n) == hipSuccess &&
             hipMalloc(&ctx->d_errflag, sizeof(int)) == hipSuccess &&
             hipMalloc(&ctx->d_diag, sizeof(double) * H9G_NDIAG) == hipSuccess &&
             hipMalloc(&ctx->d_gid, sizeof(int64_t) * n) == hipSuccess &&
@@ -1517,10 +1413,10 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
             hipMalloc(&ctx->d_perm2, sizeof(int) * ctx->ios) == hipSuccess &&
             hipMalloc(&ctx->d_hist, sizeof(int) * n) == hipSuccess;
   if (ok) {
-    ok = hipMemset(ctx->d_err, 0, sizeof(int) * 4 * n) == hipSuccess &&
+    ok = hipMemset(ctx->d_err, 0, sizeof(int) * STOP_ROWS * n) == hipSuccess &&
          hipMemset(ctx->d_errflag, 0, sizeof(int)) == hipSuccess &&
          hipMemset(ctx->d_diag, 0, sizeof(double) * H9G_NDIAG) == hipSuccess &&
-         hipMemset(ctx->d_ann, 0xff, sizeof(float) * (12 + L) * n) == hipSuccess &&
+         hipMemset(ctx->d_ann, 0xff, sizeof(float) * annual_rows(L) * n) == hipSuccess &&
          hipMemset(ctx->d_hist, 0xff, sizeof(int) * n) == hipSuccess;
   }
   ctx->slot_days.assign(cfg->nslots, 0);
@@ -1544,23 +1440,6 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
     h9g_destroy(ctx);
     return nullptr;
   }
-  static const char *names[7][2][3] = {
-      {{"", "", ""}, {"", "", ""}},
-      {{"h9g_pair_kernel<8,GeoR>", "h9g_pair_kernel<8,GeoC<8,24>>", "h9g_pair_kernel<8,GeoC<8,48>>"},
-       {"h9g_pair_kernel<10,GeoR>", "h9g_pair_kernel<10,GeoC<10,24>>", "h9g_pair_kernel<10,GeoC<10,48>>"}},
-      {{"h9g_solo_kernel<8,GeoR>", "h9g_solo_kernel<8,GeoC<8,24>>", "h9g_solo_kernel<8,GeoC<8,48>>"},
-       {"h9g_solo_kernel<10,GeoR>", "h9g_solo_kernel<10,GeoC<10,24>>", "h9g_solo_kernel<10,GeoC<10,48>>"}},
-      {{"h9g_solo_kernel<8,GeoR>+h9g_pair_kernel<8,GeoR>", "h9g_solo_kernel<8,GeoC<8,24>>+h9g_pair_kernel<8,GeoC<8,24>>",
-        "h9g_solo_kernel<8,GeoC<8,48>>+h9g_pair_kernel<8,GeoC<8,48>>"},
-       {"h9g_solo_kernel<10,GeoR>+h9g_pair_kernel<10,GeoR>",
-        "h9g_solo_kernel<10,GeoC<10,24>>+h9g_pair_kernel<10,GeoC<10,24>>",
-        "h9g_solo_kernel<10,GeoC<10,48>>+h9g_pair_kernel<10,GeoC<10,48>>"}},
-      {{"", "", ""},
-       {"h9g_pair2_kernel<10,GeoR>", "h9g_pair2_kernel<10,GeoC<10,24>>", "h9g_pair2_kernel<10,GeoC<10,48>>"}},
-      {{"h9g_pair11_kernel<8,GeoR>", "h9g_pair11_kernel<8,GeoC<8,24>>", "h9g_pair11_kernel<8,GeoC<8,48>>"},
-       {"h9g_pair11_kernel<10,GeoR>", "h9g_pair11_kernel<10,GeoC<10,24>>", "h9g_pair11_kernel<10,GeoC<10,48>>"}},
-      {{"h9g_pair1_kernel<8,GeoR>", "h9g_pair1_kernel<8,GeoC<8,24>>", "h9g_pair1_kernel<8,GeoC<8,48>>"},
-       {"h9g_pair1_kernel<10,GeoR>", "h9g_pair1_kernel<10,GeoC<10,24>>", "h9g_pair1_kernel<10,GeoC<10,48>>"}}};
   // default: the pair kernel at L = 8; at L = 10 the kernel that needs less
   // time for this many columns (l10_kind)
   if (const char *se = getenv("H9G_SORT")) ctx->sort = atoi(se) != 0;
@@ -1584,29 +1463,30 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
       said = true;
     }
   }
-  if (kenv && strcmp(kenv, "solo") == 0)
-    ctx->kind = 2;
-  else if (kenv && strcmp(kenv, "pair") == 0)
-    ctx->kind = 1;
-  else if (kenv && strcmp(kenv, "pair2") == 0 && L == 10)
-    ctx->kind = 4;
-  else if (kenv && strcmp(kenv, "pair11") == 0)
-    ctx->kind = 5;
-  else if (kenv && strcmp(kenv, "pair1") == 0)   // the one-column kernel for every launch (tests, probes)
-    ctx->kind = 6;
-  else if (kenv && strcmp(kenv, "mixed") == 0) {
+  // H9G_KERNEL names a kind (pair2: L = 10 only); else the pair kernel at L = 8 and l10_kind's choice at L = 10
+  Kind forced = K_NSTAT;
+  for (int k = K_PAIR; kenv && k < K_PROBE; k++)
+    if (strcmp(kenv, kind_info(k).env) == 0 && (k != K_PAIR2 || L == 10)) forced = (Kind)k;
+  if (forced == K_MIXED) {
     // forced split (tests): H9G_SPLIT cells on the solo kernel, else the model's
-    ctx->kind = 3;
+    ctx->kind = K_MIXED;
     size_t ns = 0;
     (void)l10_kind(n, ncu, &ns);
     if (const char *sp = getenv("H9G_SPLIT")) ns = (size_t)strtoull(sp, nullptr, 10);
     ctx->n_solo = std::min(ns, n);
-  } else if (L == 8)
-    ctx->kind = 1;
+  } else if (forced != K_NSTAT)
+    ctx->kind = forced;
+  else if (L == 8)
+    ctx->kind = K_PAIR;
   else
     ctx->kind = l10_kind(n, ncu, &ctx->n_solo);
+  // "h9g_pair_kernel<8,GeoC<8,48>>"; the mixed kind: its solo kernel + its pair kernel.  Every kernel is
+  // named h9g_<its H9G_KERNEL value>_kernel: KindInfo::env spells both (hybrid9_amd kind_id reads the prefix)
   const GeoKind gk = geo_kind(*cfg);
-  ctx->kname = names[ctx->kind][L == 8 ? 0 : 1][gk == GEO_R ? 0 : (gk == GEO_C24 ? 1 : 2)];
+  const std::string targs = "<" + std::to_string(L) + "," +
+                            (gk == GEO_R ? "GeoR" : "GeoC<" + std::to_string(L) + "," + std::to_string((int)gk) + ">") + ">";
+  auto kernel_name = [&](int k) { return "h9g_" + std::string(kind_info(k).env) + "_kernel" + targs; };
+  ctx->kname = ctx->kind == K_MIXED ? kernel_name(K_SOLO) + "+" + kernel_name(K_PAIR) : kernel_name(ctx->kind);
   return ctx;
 }
 
@@ -1616,12 +1496,12 @@ int h9g_set_params(h9g_ctx *ctx, const float *theta_s, const float *hksat, const
   if (!ctx || !theta_s || !hksat || !bsw || !psi_s || !fmax) return H9G_EINVAL;
   const size_t n = ctx->n;
   const int L = ctx->L;
-  std::vector<float> rows((4 * L + 1) * n);
+  std::vector<float> rows(par_rows(L) * n);
   const float *src[4] = {theta_s, hksat, bsw, psi_s};
   for (int k = 0; k < 4; k++)
     for (size_t c = 0; c < n; c++)
-      for (int i = 0; i < L; i++) rows[(size_t)(k * L + i) * n + c] = src[k][c * L + i];
-  memcpy(&rows[(size_t)(4 * L) * n], fmax, sizeof(float) * n);
+      for (int i = 0; i < L; i++) rows[(size_t)par_row(L, k, i) * n + c] = src[k][c * L + i];
+  memcpy(&rows[(size_t)fmax_row(L) * n], fmax, sizeof(float) * n);
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemcpyAsync(ctx->d_par, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, ctx->sc));
   HIPCHK(hipStreamSynchronize(ctx->sc));
@@ -1634,15 +1514,15 @@ int h9g_get_params(h9g_ctx *ctx, float *theta_s, float *hksat, float *bsw, float
   if (!ctx || !theta_s || !hksat || !bsw || !psi_s || !fmax) return H9G_EINVAL;
   const size_t n = ctx->n;
   const int L = ctx->L;
-  std::vector<float> rows((4 * L + 1) * n);
+  std::vector<float> rows(par_rows(L) * n);
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   HIPCHK(hipMemcpy(rows.data(), ctx->d_par, sizeof(float) * rows.size(), hipMemcpyDeviceToHost));
   float *dst[4] = {theta_s, hksat, bsw, psi_s};
   for (int k = 0; k < 4; k++)
     for (size_t c = 0; c < n; c++)
-      for (int i = 0; i < L; i++) dst[k][c * L + i] = rows[(size_t)(k * L + i) * n + c];
-  memcpy(fmax, &rows[(size_t)(4 * L) * n], sizeof(float) * n);
+      for (int i = 0; i < L; i++) dst[k][c * L + i] = rows[(size_t)par_row(L, k, i) * n + c];
+  memcpy(fmax, &rows[(size_t)fmax_row(L) * n], sizeof(float) * n);
   return 0;
 }
 
@@ -1653,7 +1533,7 @@ int h9g_init_state(h9g_ctx *ctx) {
   const int n = (int)ctx->n;
   H9G_DISPATCH(ctx, h9g_init_kernel, nblocks(n), H9G_BLOCK, ctx->sc, n, ctx->d_par, ctx->d_st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int) * 4 * ctx->n, ctx->sc));
+  HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int) * STOP_ROWS * ctx->n, ctx->sc));
   HIPCHK(hipMemsetAsync(ctx->d_errflag, 0, sizeof(int), ctx->sc));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   HIPCHK(hipMemsetAsync(ctx->d_hist, 0xff, sizeof(int) * ctx->n, ctx->sc));   // a new state has no last year
@@ -1663,28 +1543,15 @@ int h9g_init_state(h9g_ctx *ctx) {
   return 0;
 }
 
-// packed (field-major, width-fastest) <-> device rows
-static void widths(int L, int *w) {
-  const int ws[12] = {L, L, L, L + 1, 1, 1, 1, 1, 1, 1, 1, 1};
-  for (int k = 0; k < 12; k++) w[k] = ws[k];
-}
-
+// packed (field-major, width-fastest) <-> device rows: h9g_rows.h
 int h9g_set_state(h9g_ctx *ctx, const float *packed) {
   if (!ctx || !packed) return H9G_EINVAL;
   const size_t n = ctx->n;
-  int w[12];
-  widths(ctx->L, w);
   std::vector<float> rows((size_t)h9g_state_size(ctx->L) * n);
-  size_t off = 0, row = 0;
-  for (int k = 0; k < 12; k++) {
-    for (size_t c = 0; c < n; c++)
-      for (int i = 0; i < w[k]; i++) rows[(row + i) * n + c] = packed[off + c * w[k] + i];
-    off += n * w[k];
-    row += w[k];
-  }
+  state_rows_from_packed(ctx->L, n, packed, rows.data());
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemcpyAsync(ctx->d_st, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, ctx->sc));
-  HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int) * 4 * n, ctx->sc));
+  HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int) * STOP_ROWS * n, ctx->sc));
   HIPCHK(hipMemsetAsync(ctx->d_errflag, 0, sizeof(int), ctx->sc));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   HIPCHK(hipMemsetAsync(ctx->d_hist, 0xff, sizeof(int) * ctx->n, ctx->sc));   // a new state has no last year
@@ -1697,19 +1564,11 @@ int h9g_set_state(h9g_ctx *ctx, const float *packed) {
 int h9g_get_state(h9g_ctx *ctx, float *packed) {
   if (!ctx || !packed) return H9G_EINVAL;
   const size_t n = ctx->n;
-  int w[12];
-  widths(ctx->L, w);
   std::vector<float> rows((size_t)h9g_state_size(ctx->L) * n);
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   HIPCHK(hipMemcpy(rows.data(), ctx->d_st, sizeof(float) * rows.size(), hipMemcpyDeviceToHost));
-  size_t off = 0, row = 0;
-  for (int k = 0; k < 12; k++) {
-    for (size_t c = 0; c < n; c++)
-      for (int i = 0; i < w[k]; i++) packed[off + c * w[k] + i] = rows[(row + i) * n + c];
-    off += n * w[k];
-    row += w[k];
-  }
+  state_packed_from_rows(ctx->L, n, rows.data(), packed);
   return 0;
 }
 
@@ -1760,14 +1619,6 @@ static int join_prefetch(h9g_ctx *ctx, int slot) {
   return rc;
 }
 
-// Columns per wave of a pair-kernel kind: 22, 11 (kind 5, h9g_pair11_kernel)
-// or 1 (kind 6, h9g_pair1_kernel); 4 waves per workgroup.
-// Launch-statistics row of the cell order's day-1 probes (h9g_launch_stats)
-#define H9G_KIND_PROBE 7
-static int pair_wave_cols(int kind) { return kind == 5 ? H9G_PCPW11 : (kind == 6 ? 1 : H9G_PCPW); }
-static size_t pair_block_cells(int kind) { return (size_t)pair_wave_cols(kind) * H9G_PWAVES; }
-// Workgroups of a pair-kernel kind resident per CU (= waves per SIMD).
-static int pair_kind_resident(int kind) { return kind == 4 ? 2 : (kind == 6 ? 1 : pair_resident<8>()); }
 // Lists of at most this many cells (the cell-order re-runs' tails) run on
 // h9g_pair1_kernel: every workgroup resident at one wave per SIMD.
 #define H9G_PAIR1_MAX 1024
@@ -1776,20 +1627,21 @@ static int pair_kind_resident(int kind) { return kind == 4 ? 2 : (kind == 6 ? 1 
 // a later round starts hundreds of days behind the waves it shares a SIMD with.
 static int pace_mode(const h9g_ctx *ctx, int kind, size_t blocks) {
   if (ctx->prio_mode >= 0) return ctx->prio_mode;
-  return blocks <= (size_t)ctx->ncu * pair_kind_resident(kind) ? 2 : 1;
+  return blocks <= (size_t)ctx->ncu * kind_info(kind).resident ? 2 : 1;
 }
 
 // Whether a year launch of `base` cells on the context's kernel can carry k
 // more cells in a second group for free: a pair kernel kind, and the extra
 // waves fit the launch's last round of resident workgroups.
 static bool g2_fits(const h9g_ctx *ctx, size_t base, size_t k) {
-  if (k == 0 || !ctx->sort || !(ctx->kind == 1 || ctx->kind == 4 || ctx->kind == 5)) return false;
+  const KindInfo ki = kind_info(ctx->kind);
+  if (k == 0 || !ctx->sort || !ki.second_group) return false;
 #if defined(H9G_DUMP_AQ)
   return false;
 #endif
-  const size_t C = (size_t)pair_wave_cols(ctx->kind), per = pair_block_cells(ctx->kind);
+  const size_t C = (size_t)ki.wave_cols, per = (size_t)ki.block_cells;
   if (round_up(base, C) + k > ctx->ios) return false;
-  const size_t slots = (size_t)ctx->ncu * pair_kind_resident(ctx->kind);
+  const size_t slots = (size_t)ctx->ncu * ki.resident;
   const size_t b1 = (base + per - 1) / per, b2 = (round_up(base, C) + k + per - 1) / per;
   return (b2 + slots - 1) / slots == (b1 + slots - 1) / slots;
 }
@@ -1847,11 +1699,55 @@ struct YearSpec {
 // 132.5 / 67.9, pair11 120.0 / 62.3; 20,000 cells 133.6 / 68.5 against
 // 136.3 / 70.3.
 #define H9G_PAIR11_LIST 16384
-static int list_kind(const h9g_ctx *ctx, int m) {
-  if (ctx->kind == 2) return 2;
-  if (m <= H9G_PAIR1_MAX && !getenv("H9G_NO_PAIR1")) return 6;
-  if (ctx->L == 8 && ctx->kind == 1 && m <= H9G_PAIR11_LIST && !getenv("H9G_NO_PAIR11")) return 5;
-  return ctx->kind == 3 ? 1 : ctx->kind;
+static Kind list_kind(const h9g_ctx *ctx, int m) {
+  if (ctx->kind == K_SOLO) return K_SOLO;
+  if (m <= H9G_PAIR1_MAX && !getenv("H9G_NO_PAIR1")) return K_PAIR1;
+  if (ctx->L == 8 && ctx->kind == K_PAIR && m <= H9G_PAIR11_LIST && !getenv("H9G_NO_PAIR11")) return K_PAIR11;
+  return kind_info(ctx->kind).pair_part;
+}
+
+// The launch ranges of an every-cell year on the context's kernel: cells
+// [c0, cend) in workgroups of cpb cells.  One range, or for the mixed kind
+// [0, n_solo) in solo blocks and [n_solo, n) in pair blocks.
+struct LaunchRange { int c0, cend, cpb; Kind kind; };
+static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
+  const int n = (int)ctx->n, ns = (int)ctx->n_solo, cpb = kind_info(ctx->kind).block_cells;
+  int k = 0;
+  if (ctx->kind != K_MIXED) {
+    r[k++] = {0, n, cpb, ctx->kind};
+  } else {
+    if (ns > 0) r[k++] = {0, ns, H9G_YBLOCK, K_SOLO};
+    if (ns < n) r[k++] = {ns, n, cpb, K_PAIR};
+  }
+  return k;
+}
+
+// The year kernel of a launch of `kind` over a's slots: `blocks` workgroups
+// of its pair part; the mixed kind over year_ranges' two.
+static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks) {
+  const unsigned pb = (unsigned)blocks, pt = 64 * H9G_PWAVES;
+  switch (kind) {
+    case K_SOLO:   // (no second group on the solo kernel: [c0, cend) is the launch)
+      H9G_DISPATCH(ctx, h9g_solo_kernel, (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK), H9G_YBLOCK,
+                   ctx->sc, a);
+      break;
+    case K_MIXED: {
+      LaunchRange r[2];
+      const int nr = year_ranges(ctx, r);
+      for (int i = 0; i < nr; i++) {
+        a.c0 = r[i].c0;
+        a.cend = a.bend = a.split = r[i].cend;
+        if (int rc = launch_year(ctx, r[i].kind, a, blocks)) return rc;
+      }
+      return 0;
+    }
+    case K_PAIR2: H9G_DISPATCH_L10(ctx, h9g_pair2_kernel, pb, pt, ctx->sc, a); break;
+    case K_PAIR11: H9G_DISPATCH(ctx, h9g_pair11_kernel, pb, pt, ctx->sc, a); break;
+    case K_PAIR1: H9G_DISPATCH(ctx, h9g_pair1_kernel, pb, pt, ctx->sc, a); break;
+    default: H9G_DISPATCH(ctx, h9g_pair_kernel, pb, pt, ctx->sc, a); break;
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
@@ -1859,7 +1755,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   const int m = ys.m;
   if (!ctx || ys.slot < 0 || ys.slot >= ctx->cfg.nslots || ys.jyear < 1861 || ys.jyear > 2299) return H9G_EINVAL;
   if (d_list && (m < 1 || (size_t)m > ctx->n || !ys.ann_dst)) return H9G_EINVAL;
-  if (ys.bulk && (!d_list || ys.st || ctx->kind == 2 || ctx->kind == 3)) return H9G_EINVAL;
+  if (ys.bulk && (!d_list || ys.st || ctx->kind == K_SOLO || ctx->kind == K_MIXED)) return H9G_EINVAL;
   if (ys.probe && (!d_list || ys.bulk || !ys.st || ys.k2 > 0 || ys.ndays < 1)) return H9G_EINVAL;
   const bool two = ys.k2 > 0;
   if (two && ((d_list && !ys.bulk) || !ys.h2 || !ys.st2 || !ys.err2 || !ys.ann2 || ys.slot2 < 0 ||
@@ -1906,20 +1802,21 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   a.err2 = a.err;
   a.iostride = ios;
   a.raw = ys.probe ? 1 : 0;
-  const int kind = d_list && !ys.bulk ? list_kind(ctx, m) : ctx->kind;
+  const Kind kind = d_list && !ys.bulk ? list_kind(ctx, m) : ctx->kind;
+  const KindInfo ki = kind_info(kind);
   const size_t ncells = d_list ? (size_t)m : ctx->n;
   // slot-ordered forcing and annual sums (row stride ios: the cells plus a
   // second group's slack)
   if (d_list || ctx->sort) {
     if (!ctx->d_forc_s) HIPCHK(hipMalloc(&ctx->d_forc_s, sizeof(float) * 7 * (size_t)ctx->cfg.max_days * ios));
-    if (!ctx->d_ann_s) HIPCHK(hipMalloc(&ctx->d_ann_s, sizeof(float) * (12 + ctx->L) * ios));
+    if (!ctx->d_ann_s) HIPCHK(hipMalloc(&ctx->d_ann_s, sizeof(float) * annual_rows(ctx->L) * ios));
   }
   const size_t dvar = (size_t)ctx->cfg.max_days * ios;
   // the second group from the first whole wave after the first group's
   // cells: its slots of d_perm (in h9g_sort_kernel's order over its own
   // state), then its year's forcing into them
   auto second_group = [&](int base, int pcpb) -> int {
-    const int split = (int)round_up((size_t)base, (size_t)pair_wave_cols(kind));
+    const int split = (int)round_up((size_t)base, (size_t)ki.wave_cols);
     HIPCHK(hipMemcpyAsync(ctx->d_perm2 + split, ys.h2, sizeof(int) * ys.k2, hipMemcpyHostToDevice, ctx->sc));
     H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, split, split + ys.k2, pcpb, ys.st2,
                  ys.err2, ctx->d_hist, ctx->hist_nsub, ctx->d_perm, ctx->d_perm2);
@@ -1935,9 +1832,9 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     return 0;
   };
   if (d_list) {
-    const int pcpb = kind == 2 ? H9G_YBLOCK : (int)pair_block_cells(kind);
+    const int pcpb = ki.block_cells;
     a.perm = d_list;
-    if (ctx->sort && kind != 6) {
+    if (ctx->sort && kind != K_PAIR1) {
       // the list in h9g_sort_kernel's order (its waves' columns take the
       // same branches), into d_perm, free between every-cell launches
       H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, 0, m, pcpb, a.st, a.err, ctx->d_hist,
@@ -1953,41 +1850,22 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     a.annual = ctx->d_ann_s;
     a.sorted_io = 1;
   } else if (ctx->sort) {             // per launch range and its workgroup size (h9g_sort_kernel)
-    const int ns = (int)ctx->n_solo, pcpb = (int)pair_block_cells(ctx->kind);
-    if (ctx->kind == 2) {
-      H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, 0, n, H9G_YBLOCK, ctx->d_st, ctx->d_err,
-                   ctx->d_hist, ctx->hist_nsub, ctx->d_perm, nullptr);
-    } else if (ctx->kind == 3) {
-      if (ns > 0)
-        H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, 0, ns, H9G_YBLOCK, ctx->d_st,
-                     ctx->d_err, ctx->d_hist, ctx->hist_nsub, ctx->d_perm, nullptr);
-      if (ns < n)
-        H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, ns, n, pcpb, ctx->d_st, ctx->d_err,
-                     ctx->d_hist, ctx->hist_nsub, ctx->d_perm, nullptr);
-    } else {
-      H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, 0, n, pcpb, ctx->d_st, ctx->d_err,
-                   ctx->d_hist, ctx->hist_nsub, ctx->d_perm, nullptr);
-    }
+    LaunchRange r[2];
+    const int nr = year_ranges(ctx, r);
+    for (int i = 0; i < nr; i++)
+      H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, r[i].c0, r[i].cend, r[i].cpb, ctx->d_st,
+                   ctx->d_err, ctx->d_hist, ctx->hist_nsub, ctx->d_perm, nullptr);
     HIPCHK(hipGetLastError());
     a.perm = ctx->d_perm;
 #if !defined(H9G_DUMP_AQ)                 // (that record is indexed by the annual array's cell)
     // forcing and annual sums in slot order for the year kernel, per launch
     // range with its workgroup size, as the sort above
-    auto perm_range = [&](int c0, int cend, int cpb, int ntr, const float *src) {
-      h9g_perm_forcing_kernel<<<perm_forcing_blocks(c0, cend, cpb, ntr), 256, 0, ctx->sc>>>(
-          c0, cend, cpb, ntr, n, a.fvar, ios, dvar, ctx->d_perm, src, ctx->d_forc_s);
-    };
-    if (ctx->kind == 2) {
-      perm_range(0, n, H9G_YBLOCK, nt, a.forc);
-    } else if (ctx->kind == 3) {
-      if (ns > 0) perm_range(0, ns, H9G_YBLOCK, nt, a.forc);
-      if (ns < n) perm_range(ns, n, pcpb, nt, a.forc);
-    } else {
-      perm_range(0, n, pcpb, nt, a.forc);
-    }
+    for (int i = 0; i < nr; i++)
+      h9g_perm_forcing_kernel<<<perm_forcing_blocks(r[i].c0, r[i].cend, r[i].cpb, nt), 256, 0, ctx->sc>>>(
+          r[i].c0, r[i].cend, r[i].cpb, nt, n, a.fvar, ios, dvar, ctx->d_perm, a.forc, ctx->d_forc_s);
     HIPCHK(hipGetLastError());
     if (two)
-      if (int r = second_group(n, pcpb)) return r;
+      if (int rc = second_group(n, ki.block_cells)) return rc;
     a.forc = ctx->d_forc_s;
     a.annual = ctx->d_ann_s;
     a.sorted_io = 1;
@@ -1995,10 +1873,10 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   }
   if (a.sorted_io) a.fvar = dvar;
   // workgroups of the launch (the pair part's, for the mixed kind)
-  const size_t per_block = kind == 2 ? (size_t)H9G_YBLOCK : pair_block_cells(kind == 3 ? 1 : kind);
-  const size_t blocks = kind == 3 ? (ctx->n - ctx->n_solo + per_block - 1) / per_block
-                                  : ((size_t)a.cend + per_block - 1) / per_block;
-  if (kind != 2) {
+  const size_t per_block = (size_t)ki.block_cells;
+  const size_t blocks = kind == K_MIXED ? (ctx->n - ctx->n_solo + per_block - 1) / per_block
+                                        : ((size_t)a.cend + per_block - 1) / per_block;
+  if (ki.pair) {
     // the pair kernels' day-snapshot blocks, one per workgroup of the launch
     const size_t need = std::max<size_t>(blocks, 1) * PairStore<8, H9G_PLANES>::GBLOCK;
     if (ctx->sv_bytes < need) {
@@ -2017,7 +1895,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   }
   a.pace = ctx->d_pace;
   a.epoch = ++ctx->epoch;
-  a.prio_mode = pace_mode(ctx, kind == 3 ? 1 : kind, blocks);
+  a.prio_mode = pace_mode(ctx, kind, blocks);
 #if defined(H9G_STAMPS)
   {  // one record of 8 words per wave of the launch
     const size_t words = (size_t)8 * H9G_PWAVES * (blocks + 1);
@@ -2057,41 +1935,15 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   }
 #endif
   const int e = ctx->nev++;
-  ctx->ev_kind[e] = ys.probe ? H9G_KIND_PROBE : kind;
+  ctx->ev_kind[e] = ys.probe ? K_PROBE : kind;
   ctx->ev_cells[e] = (int64_t)ncells + (two ? ys.k2 : 0);
   HIPCHK(hipEventRecord(ctx->ev0[e], ctx->sc));
-  if (kind == 2) {
-    H9G_DISPATCH(ctx, h9g_solo_kernel, (unsigned)((ncells + H9G_YBLOCK - 1) / H9G_YBLOCK), H9G_YBLOCK,
-                 ctx->sc, a);
-  } else if (kind == 3) {
-    // mixed (l10_kind): whole rounds of solo waves, then the pair kernel on the rest
-    const size_t ns = ctx->n_solo;
-    if (ns > 0) {
-      a.c0 = 0;
-      a.cend = a.bend = a.split = (int)ns;
-      H9G_DISPATCH(ctx, h9g_solo_kernel, (unsigned)((ns + H9G_YBLOCK - 1) / H9G_YBLOCK), H9G_YBLOCK,
-                   ctx->sc, a);
-    }
-    if (ns < ctx->n) {
-      a.c0 = (int)ns;
-      a.cend = a.bend = a.split = (int)ctx->n;
-      H9G_DISPATCH(ctx, h9g_pair_kernel, (unsigned)blocks, 64 * H9G_PWAVES, ctx->sc, a);
-    }
-  } else if (kind == 4) {
-    H9G_DISPATCH_L10(ctx, h9g_pair2_kernel, (unsigned)blocks, 64 * H9G_PWAVES, ctx->sc, a);
-  } else if (kind == 5) {
-    H9G_DISPATCH(ctx, h9g_pair11_kernel, (unsigned)blocks, 64 * H9G_PWAVES, ctx->sc, a);
-  } else if (kind == 6) {
-    H9G_DISPATCH(ctx, h9g_pair1_kernel, (unsigned)blocks, 64 * H9G_PWAVES, ctx->sc, a);
-  } else {
-    H9G_DISPATCH(ctx, h9g_pair_kernel, (unsigned)blocks, 64 * H9G_PWAVES, ctx->sc, a);
-  }
-  HIPCHK(hipGetLastError());
+  if (int r = launch_year(ctx, kind, a, blocks)) return r;
   HIPCHK(hipEventRecord(ctx->ev1[e], ctx->sc));
   HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot], ctx->sc));
   if (two) HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot2], ctx->sc));
   if (a.sorted_io) {
-    const unsigned rows = (unsigned)(12 + ctx->L);
+    const unsigned rows = (unsigned)annual_rows(ctx->L);
     h9g_unperm_annual_kernel<<<dim3((unsigned)((ncells + 255) / 256), rows), 256, 0, ctx->sc>>>(
         (int)ncells, n, (int)rows, 0, ios, a.perm, ctx->d_ann_s, d_list ? ys.ann_dst : ctx->d_ann);
     if (two)
@@ -2335,14 +2187,14 @@ static int ord_alloc(h9g_ctx *ctx, int ny) {
   ord_free(ctx);
   ctx->ord = new OrdBufs();
   OrdBufs *o = ctx->ord;
-  const size_t n = ctx->n, L = (size_t)ctx->L, srows = (size_t)h9g_state_size(ctx->L), rows = 12 + L;
+  const size_t n = ctx->n, L = (size_t)ctx->L, srows = (size_t)h9g_state_size(ctx->L), rows = annual_rows(ctx->L);
   bool ok = hipMalloc(&o->st2, sizeof(float) * srows * n) == hipSuccess &&
-            hipMalloc(&o->err2, sizeof(int) * 4 * n) == hipSuccess &&
+            hipMalloc(&o->err2, sizeof(int) * STOP_ROWS * n) == hipSuccess &&
             hipMalloc(&o->d_bulk, sizeof(int) * (n + 1)) == hipSuccess &&
             hipMalloc(&o->gold, sizeof(float) * L * n) == hipSuccess &&
             hipMalloc(&o->pst, sizeof(float) * 2 * srows * n) == hipSuccess &&
             hipMalloc(&o->pann, sizeof(float) * 2 * rows * n) == hipSuccess &&
-            hipMalloc(&o->perr, sizeof(int) * 2 * 4 * n) == hipSuccess &&
+            hipMalloc(&o->perr, sizeof(int) * 2 * STOP_ROWS * n) == hipSuccess &&
             hipMalloc(&o->d_plist, sizeof(int) * (n + 1)) == hipSuccess &&
             hipMalloc(&o->d_pkeep, sizeof(int) * (n + 1)) == hipSuccess;
   for (OrdDec &D : o->d) {
@@ -2350,8 +2202,8 @@ static int ord_alloc(h9g_ctx *ctx, int ny) {
          hipMalloc(&D.guess, sizeof(float) * L * n) == hipSuccess &&
          hipMalloc(&D.ann, sizeof(float) * (size_t)ny * rows * n) == hipSuccess &&
          hipMalloc(&D.ck, sizeof(float) * (size_t)ny * srows * n) == hipSuccess &&
-         hipMalloc(&D.err0, sizeof(int) * 4 * n) == hipSuccess &&
-         hipMalloc(&D.eck, sizeof(int) * (size_t)ny * 4 * n) == hipSuccess &&
+         hipMalloc(&D.err0, sizeof(int) * STOP_ROWS * n) == hipSuccess &&
+         hipMalloc(&D.eck, sizeof(int) * (size_t)ny * STOP_ROWS * n) == hipSuccess &&
          hipMalloc(&D.dirty, sizeof(int) * n) == hipSuccess;
     for (int **p : {&D.d_chain, &D.d_pred, &D.d_first, &D.d_list, &D.d_flag})
       ok = ok && hipMalloc(p, sizeof(int) * (n + 1)) == hipSuccess;
@@ -2375,8 +2227,8 @@ struct OrdStats {
 static float *ord_ck(const h9g_ctx *ctx, const OrdDec &D, int y) {
   return D.ck + (size_t)y * h9g_state_size(ctx->L) * ctx->n;
 }
-static int *ord_eck(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.eck + (size_t)y * 4 * ctx->n; }
-static float *ord_ann(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.ann + (size_t)y * (12 + ctx->L) * ctx->n; }
+static int *ord_eck(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.eck + (size_t)y * STOP_ROWS * ctx->n; }
+static float *ord_ann(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.ann + (size_t)y * annual_rows(ctx->L) * ctx->n; }
 
 // The decade's chains (h9g_set_chains) over its land cells that have not
 // stopped when it starts (its final err0), in context order: predecessors
@@ -2430,11 +2282,11 @@ static int ord_chain(h9g_ctx *ctx, OrdDec &D, const std::vector<char> &land) {
 static int ord_probe(h9g_ctx *ctx, OrdDec &D, const int32_t *slots, const std::vector<int> &cand, OrdStats &S) {
   OrdBufs *o = ctx->ord;
   const int n = (int)ctx->n, L = ctx->L, k = (int)cand.size();
-  const int rows = 12 + L, srows = h9g_state_size(L);
+  const int rows = annual_rows(L), srows = h9g_state_size(L);
   HIPCHK(hipMemcpyAsync(o->d_plist, cand.data(), sizeof(int) * k, hipMemcpyHostToDevice, ctx->sc));
   for (int v = 0; v < 2; v++) {
     float *st = o->pst + (size_t)v * srows * n;
-    int *err = o->perr + (size_t)v * 4 * n;
+    int *err = o->perr + (size_t)v * STOP_ROWS * n;
     h9g_restart_kernel<<<(unsigned)((k + 255) / 256), 256, 0, ctx->sc>>>(k, n, L, o->d_plist, D.st0, D.err0,
                                                                         v ? D.guess : o->gold, st, err);
     HIPCHK(hipGetLastError());
@@ -2451,7 +2303,7 @@ static int ord_probe(h9g_ctx *ctx, OrdDec &D, const int32_t *slots, const std::v
     if (int r = run_year_impl(ctx, ys)) return r;
   }
   h9g_probe_cmp_kernel<<<(unsigned)((k + 255) / 256), 256, 0, ctx->sc>>>(
-      k, n, srows, rows, o->d_plist, o->pst, o->pst + (size_t)srows * n, o->perr, o->perr + (size_t)4 * n, o->pann,
+      k, n, srows, rows, o->d_plist, o->pst, o->pst + (size_t)srows * n, o->perr, o->perr + (size_t)STOP_ROWS * n, o->pann,
       o->pann + (size_t)rows * n, o->d_pkeep);
   HIPCHK(hipGetLastError());
   std::vector<int> keep(k);
@@ -2570,14 +2422,14 @@ static int ord_settle(h9g_ctx *ctx, OrdDec &D, const int32_t *slots, OrdStats &S
 // states into N's start (h9g_settle_kernel).
 static int ord_finish(h9g_ctx *ctx, OrdDec &D, OrdDec *N, float *annual, int &stop_seen) {
   const size_t n = ctx->n;
-  const int rows = 12 + ctx->L, srows = h9g_state_size(ctx->L);
+  const int rows = annual_rows(ctx->L), srows = h9g_state_size(ctx->L);
   if (annual)
     HIPCHK(hipMemcpyAsync(annual + (size_t)D.k0 * rows * n, D.ann, sizeof(float) * (size_t)D.ny * rows * n,
                           hipMemcpyDeviceToHost, ctx->sc));
   if (!stop_seen && ctx->last_err.code == 0) {
-    std::vector<int> e0(n), e1(4 * n);
+    std::vector<int> e0(n), e1(STOP_ROWS * n);
     HIPCHK(hipMemcpyAsync(e0.data(), D.err0, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->sc));
-    HIPCHK(hipMemcpyAsync(e1.data(), ord_eck(ctx, D, D.ny - 1), sizeof(int) * 4 * n, hipMemcpyDeviceToHost, ctx->sc));
+    HIPCHK(hipMemcpyAsync(e1.data(), ord_eck(ctx, D, D.ny - 1), sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToHost, ctx->sc));
     HIPCHK(hipStreamSynchronize(ctx->sc));
     for (size_t c = 0; c < n; c++) {
       if (e1[c] == 0 || e0[c] != 0) continue;
@@ -2618,7 +2470,7 @@ __global__ void __launch_bounds__(256) h9g_exclude_kernel(int k, int n, int ny, 
   if (j >= k) return;
   const int c = list[j];
   dirty[c] = 1;
-  for (int y = 0; y < ny; y++) eck[(size_t)y * 4 * n + c] = -1;
+  for (int y = 0; y < ny; y++) eck[(size_t)y * STOP_ROWS * n + c] = -1;
 }
 
 // decades: (first year, years) of each decade the call runs, in order;
@@ -2643,7 +2495,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
   }
   if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
   const size_t n = ctx->n;
-  const int L = ctx->L, rows = 12 + L, srows = h9g_state_size(L);
+  const int L = ctx->L, rows = annual_rows(L), srows = h9g_state_size(L);
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   if (int r = ord_alloc(ctx, nymax)) return r;
@@ -2676,8 +2528,8 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
     D.list.clear();
     // the decade starts from the context's state as known now
     HIPCHK(hipMemcpyAsync(D.st0, ctx->d_st, sizeof(float) * srows * n, hipMemcpyDeviceToDevice, ctx->sc));
-    HIPCHK(hipMemcpyAsync(D.err0, ctx->d_err, sizeof(int) * 4 * n, hipMemcpyDeviceToDevice, ctx->sc));
-    HIPCHK(hipMemcpyAsync(D.guess, ctx->d_st + (size_t)2 * L * n, sizeof(float) * (size_t)L * n,
+    HIPCHK(hipMemcpyAsync(D.err0, ctx->d_err, sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToDevice, ctx->sc));
+    HIPCHK(hipMemcpyAsync(D.guess, ctx->d_st + (size_t)smp_row(L, 0) * n, sizeof(float) * (size_t)L * n,
                           hipMemcpyDeviceToDevice, ctx->sc));
     HIPCHK(hipMemsetAsync(D.dirty, 0, sizeof(int) * n, ctx->sc));
     // the cells P is still re-running stay out of D's first pass: their end
@@ -2731,7 +2583,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
       S.ticks++;
       HIPCHK(hipMemcpyAsync(ord_ann(ctx, D, y), ctx->d_ann, sizeof(float) * rows * n, hipMemcpyDeviceToDevice, ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_ck(ctx, D, y), ctx->d_st, sizeof(float) * srows * n, hipMemcpyDeviceToDevice, ctx->sc));
-      HIPCHK(hipMemcpyAsync(ord_eck(ctx, D, y), ctx->d_err, sizeof(int) * 4 * n, hipMemcpyDeviceToDevice, ctx->sc));
+      HIPCHK(hipMemcpyAsync(ord_eck(ctx, D, y), ctx->d_err, sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToDevice, ctx->sc));
       if (ride) {
         S.ride_steps++;
         S.ride_cell_years += ys.k2;
@@ -2777,7 +2629,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
   // the last decade's end: the context's state, STOP records and last-year means
   HIPCHK(hipMemcpyAsync(ctx->d_st, ord_ck(ctx, *P, P->ny - 1), sizeof(float) * srows * n, hipMemcpyDeviceToDevice,
                         ctx->sc));
-  HIPCHK(hipMemcpyAsync(ctx->d_err, ord_eck(ctx, *P, P->ny - 1), sizeof(int) * 4 * n, hipMemcpyDeviceToDevice, ctx->sc));
+  HIPCHK(hipMemcpyAsync(ctx->d_err, ord_eck(ctx, *P, P->ny - 1), sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToDevice, ctx->sc));
   HIPCHK(hipMemcpyAsync(ctx->d_ann, ord_ann(ctx, *P, P->ny - 1), sizeof(float) * rows * n, hipMemcpyDeviceToDevice,
                         ctx->sc));
   h9g_diag_kernel<<<1, 1024, 0, ctx->sc>>>((int)n, L, ctx->d_ann, ctx->d_st, ctx->d_err, ctx->d_diag);
@@ -2833,7 +2685,7 @@ int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, 
       if (slots[y] < 0 || slots[y] >= ctx->cfg.nslots || used[(size_t)slots[y]]++) return H9G_EINVAL;
     HIPCHK(hipSetDevice(ctx->device));
     if (int r = daily_begin(ctx, jyear0, nyears)) return r;
-    const size_t rows = 12 + (size_t)ctx->L;
+    const size_t rows = annual_rows(ctx->L);
     int first = 0, k0 = 0, i = 0;
     for (const auto &d : ref_decades(jyear0, nyears)) {
       const int r = run_ordered_impl(ctx, slots + k0, d.first, {d}, annual ? annual + (size_t)k0 * rows * ctx->n : nullptr,
@@ -2885,7 +2737,7 @@ int h9g_launch_stats(h9g_ctx *ctx, double *out, int n, int reset) {
   if (!ctx || !out || n < 1) return H9G_EINVAL;
   if (int r = fold_events(ctx)) return r;
   int m = 0;
-  for (int k = 1; k <= H9G_KIND_PROBE; k++)
+  for (int k = K_PAIR; k <= K_PROBE; k++)
     for (int j = 0; j < 3 && m < n; j++) out[m++] = ctx->kstat[k][j];
   if (reset)
     for (auto &row : ctx->kstat) row[0] = row[1] = row[2] = 0.0;
@@ -2898,8 +2750,8 @@ int h9g_sync(h9g_ctx *ctx) {
   HIPCHK(hipStreamSynchronize(ctx->sx));
   if (int r = fold_events(ctx)) return r;
 #if defined(H9G_STAMPS)
-  if (ctx->d_stamps && (ctx->kind == 1 || ctx->kind == 5 || ctx->kind == 6)) {   // mean shader cycles per wave and substep, by phase
-    const size_t cw = (size_t)pair_wave_cols(ctx->kind), nw = (ctx->n + cw - 1) / cw;
+  if (ctx->d_stamps && (ctx->kind == K_PAIR || ctx->kind == K_PAIR11 || ctx->kind == K_PAIR1)) {   // mean shader cycles per wave and substep, by phase
+    const size_t cw = (size_t)kind_info(ctx->kind).wave_cols, nw = (ctx->n + cw - 1) / cw;
     std::vector<unsigned> st(8 * nw);
     HIPCHK(hipMemcpy(st.data(), ctx->d_stamps, sizeof(unsigned) * 8 * nw, hipMemcpyDeviceToHost));
     double sum[8] = {0}, tot = 0;
@@ -2993,8 +2845,8 @@ int h9g_sync(h9g_ctx *ctx) {
   if (!flag) return 0;
   if (ctx->last_err.code == 0) {
     const size_t n = ctx->n;
-    std::vector<int> e(4 * n);
-    HIPCHK(hipMemcpy(e.data(), ctx->d_err, sizeof(int) * 4 * n, hipMemcpyDeviceToHost));
+    std::vector<int> e(STOP_ROWS * n);
+    HIPCHK(hipMemcpy(e.data(), ctx->d_err, sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToHost));
     for (size_t c = 0; c < n; c++) {
       if (e[c]) {        // lowest cell index first, as the reference's cell-outer loop
         ctx->last_err.code = e[c];
@@ -3017,7 +2869,7 @@ int h9g_run_site(h9g_ctx *ctx, int nday, const float *sub, const float *daily, c
   HIPCHK(hipStreamSynchronize(ctx->sc));
   const size_t n = ctx->n, ns = (size_t)ctx->cfg.nisurf;
   const size_t nsub = (size_t)nday * ns * 5 * n, nd = (size_t)nday * 2 * n, nl = (size_t)nday * 3 * n;
-  const size_t nout = (size_t)nday * 11 * n;
+  const size_t nout = (size_t)nday * DAILY_ROWS * n;
   float *buf = nullptr;
   HIPCHK(hipMalloc(&buf, sizeof(float) * (nsub + nd + nl + nout)));
   SiteArgs a;
@@ -3059,7 +2911,7 @@ int h9g_get_errors(h9g_ctx *ctx, int32_t *rec) {
   if (!ctx || !rec) return H9G_EINVAL;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
-  HIPCHK(hipMemcpy(rec, ctx->d_err, sizeof(int32_t) * 4 * ctx->n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rec, ctx->d_err, sizeof(int32_t) * STOP_ROWS * ctx->n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -3073,7 +2925,7 @@ int h9g_get_annual(h9g_ctx *ctx, float *annual) {
   if (!ctx || !annual) return H9G_EINVAL;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
-  HIPCHK(hipMemcpy(annual, ctx->d_ann, sizeof(float) * (12 + ctx->L) * ctx->n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(annual, ctx->d_ann, sizeof(float) * annual_rows(ctx->L) * ctx->n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -3268,7 +3120,7 @@ int h9g_soil_fmax(h9g_ctx *ctx, const int32_t *soil_tex, const int32_t *fmax, in
       fm[c] = __builtin_nanf("");
     }
   }
-  HIPCHK(hipMemcpy(ctx->d_par + (size_t)(4 * L) * n, fm.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->d_par + (size_t)fmax_row(L) * n, fm.data(), sizeof(float) * n, hipMemcpyHostToDevice));
   ctx->params_set = 1;
   return 0;
 }
@@ -3287,7 +3139,7 @@ double h9g_total_kernel_ms(h9g_ctx *ctx, int reset) {
   return t;
 }
 
-const char *h9g_kernel_name(h9g_ctx *ctx) { return ctx ? ctx->kname : ""; }
+const char *h9g_kernel_name(h9g_ctx *ctx) { return ctx ? ctx->kname.c_str() : ""; }
 
 // (h9g_build_id is defined in h9g_io.cpp, the translation unit that is
 // recompiled with every build.)

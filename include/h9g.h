@@ -108,7 +108,8 @@ int h9g_init_state(h9g_ctx *ctx);
 /* Packed per-cell state, fields in this order, each (width, ncell) with
  * width-fastest:  h2osoi_liq(L) h2osoi_liq_ma(L) smp(L) rootr_col(L+1)
  * zwt wa LAI LAI_litter plant_mass plant_foliage_mass plant_length rdepth
- * -> h9g_state_size(L) = 4L+9 floats per cell. */
+ * -> h9g_state_size(L) = 4L+9 floats per cell.  (The device keeps these as
+ * rows of ncell: hybrid9_amd/csrc/h9g_rows.h describes that layout, once.) */
 int h9g_state_size(int nlayers);
 int h9g_set_state(h9g_ctx *ctx, const float *packed);
 int h9g_get_state(h9g_ctx *ctx, float *packed);

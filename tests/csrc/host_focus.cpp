@@ -8,9 +8,11 @@
 // product library.
 #include <stdint.h>
 #include <string.h>
+#include <vector>
 #include "../../hybrid9_amd/csrc/h9g_geo.h"
 #include "../../hybrid9_amd/csrc/h9g_step.h"
 #include "../../hybrid9_amd/csrc/h9g_pair.h"
+#include "../../hybrid9_amd/csrc/h9g_rows.h"
 
 using namespace h9k;
 static const uint64_t E2[32] = H9M_EXP2F_TAB_INIT;
@@ -31,34 +33,26 @@ static int run_focus_cells(const G &g, int n, int nisurf, int grow_on, int year0
     ndays += yrs[y].nt;
   }
   int first = 0;
+  // the oracle's packed blocks as rows of n (h9g_rows.h), as the device reads them
+  std::vector<float> prow((size_t)Rows<L>::PAR * n), srow((size_t)Rows<L>::STATE * n);
+  par_rows_from_packed(L, n, par, prow.data());
+  state_rows_from_packed(L, n, st, srow.data());
 #pragma omp parallel for schedule(dynamic, 1)
   for (int c = 0; c < n; c++) {
     float store[FlatStore<L>::N], zt[zt_size<L>()];
     fill_zt<L>(g, zt);
     FlatStore<L> cs{store, zt};
     St<L> s;
-    float ts_sum = zero;
-    for (int i = 1; i <= L; i++) {
-      cs.set_lay(PF_TS, i, par[0 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_HKS, i, par[1 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_BSW, i, par[2 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_PSI, i, par[3 * n * L + c * L + i - 1]);
-      s.h2o[i] = st[0 * n * L + c * L + i - 1];
-      s.smp[i] = st[2 * n * L + c * L + i - 1];
-      cs.set_lay(PF_ROOTR, i, st[3 * n * L + c * (L + 1) + i - 1]);
-      ts_sum = ts_sum + cs.lay(PF_TS, i);
-    }
-    cs.set_sc(PS_FMAX, par[4 * n * L + c]);
+    H9K_LOAD_LANE(L, cs, s, prow.data(), n, c, srow.data(), n, c)
+    H9K_LOAD_SCALARS(L, s, srow.data(), n, c)
+    H9K_TS_SUM(L, cs, ts_sum)
     code_out[c] = 0;
-    if (!(ts_sum > 1.0E-8f) || (failed && failed[c])) {
-      for (size_t k = 0; k < (size_t)ndays * 11; k++) out[k * n + c] = __builtin_nanf("");
+    if (!(ts_sum > SOIL_TRUNC) || (failed && failed[c])) {
+      nan_rows(out, ndays * DAILY_ROWS, n, c);
       continue;
     }
     cell_inv_pair<L, G>(g, cs);
-    const float *q = st + (size_t)n * (4 * L + 1);
-    s.zwt = q[c]; s.wa = q[n + c]; s.LAI = q[2 * n + c]; s.LAI_litter = q[3 * n + c];
-    s.pm = q[4 * n + c]; s.pfm = q[5 * n + c]; s.plen = q[6 * n + c]; s.rdepth = q[7 * n + c];
-    const int code = cell_focus<L, G>(g, cs, s, st[1 * n * L + c * L], yrs, nyears, (size_t)c, (size_t)n,
+    const int code = cell_focus<L, G>(g, cs, s, srow[(size_t)Rows<L>::H2O_MA * n + c], yrs, nyears, (size_t)c, (size_t)n,
                                       (size_t)ndays * n, nisurf, grow_on, out + c, (size_t)n, T);
     code_out[c] = code;
     if (code) {

@@ -7,6 +7,7 @@
 // a GPU.  Never linked into the product library.
 #include <stdint.h>
 #include <string.h>
+#include <vector>
 // exact re-runs: count, runs replaying from a snapshot taken before substep
 // 0 of a later substep (several substeps replayed), substeps replayed
 static long long g_exact[3];
@@ -19,12 +20,28 @@ static long long g_exact[3];
 #include "../../hybrid9_amd/csrc/h9g_geo.h"
 #include "../../hybrid9_amd/csrc/h9g_step.h"
 #include "../../hybrid9_amd/csrc/h9g_pair.h"
+#include "../../hybrid9_amd/csrc/h9g_rows.h"
 
 using namespace h9k;
 static const uint64_t E2[32] = H9M_EXP2F_TAB_INIT;
 static const double L2[32] = H9M_POWF_LOG2_TAB_INIT;
 
 static int diy(int y) { return y % 4 ? 365 : (y % 100 ? 366 : (y % 400 ? 365 : 366)); }
+
+// The oracle's packed parameters and state as rows of n (h9g_rows.h), as the
+// device kernels read them; the state goes back packed when the run is done.
+template <int L>
+struct CellRows {
+  int n;
+  float *packed_st;
+  std::vector<float> par, st;
+  CellRows(int n, const float *packed_par, float *packed_st)
+      : n(n), packed_st(packed_st), par((size_t)Rows<L>::PAR * n), st((size_t)Rows<L>::STATE * n) {
+    par_rows_from_packed(L, n, packed_par, par.data());
+    state_rows_from_packed(L, n, packed_st, st.data());
+  }
+  ~CellRows() { state_packed_from_rows(L, n, st.data(), packed_st); }
+};
 
 template <int L, class G>
 static int run_cells_pair(const G &g, int n, int nisurf, int grow_on, int year0, int nyears,
@@ -33,6 +50,7 @@ static int run_cells_pair(const G &g, int n, int nisurf, int grow_on, int year0,
   int ndays = 0;
   for (int y = 0; y < nyears; y++) ndays += diy(year0 + y);
   int first = 0;
+  CellRows<L> rows(n, par, st);
 #pragma omp parallel for schedule(dynamic, 4)
   for (int c = 0; c < n; c++) {
     float store[FlatStore<L>::N], zt[zt_size<L>()];
@@ -40,24 +58,13 @@ static int run_cells_pair(const G &g, int n, int nisurf, int grow_on, int year0,
     FlatStore<L> cs{store, zt};
     const SplitAll sp;
     St<L> s;
-    for (int i = 1; i <= L; i++) {
-      cs.set_lay(PF_TS, i, par[0 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_HKS, i, par[1 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_BSW, i, par[2 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_PSI, i, par[3 * n * L + c * L + i - 1]);
-      s.h2o[i] = st[0 * n * L + c * L + i - 1];
-      s.smp[i] = st[2 * n * L + c * L + i - 1];
-      cs.set_lay(PF_ROOTR, i, st[3 * n * L + c * (L + 1) + i - 1]);
-    }
-    cs.set_sc(PS_FMAX, par[4 * n * L + c]);
+    H9K_LOAD_LANE(L, cs, s, rows.par.data(), n, c, rows.st.data(), n, c)
+    H9K_LOAD_SCALARS(L, s, rows.st.data(), n, c)
     cell_inv_pair<L, G>(g, cs);
-    float *q = st + (size_t)n * (4 * L + 1);
-    s.zwt = q[c]; s.wa = q[n + c]; s.LAI = q[2 * n + c]; s.LAI_litter = q[3 * n + c];
-    s.pm = q[4 * n + c]; s.pfm = q[5 * n + c]; s.plen = q[6 * n + c]; s.rdepth = q[7 * n + c];
     int d0 = 0;
     for (int y = 0; y < nyears; y++) {
       const int nt = diy(year0 + y);
-      float a[12 + L];
+      float a[Rows<L>::ANNUAL];
       int eday = 0, estep = 0;
       float ev = 0;
       const int code = cell_year_pair<L, G>(g, cs, sp, s, forc + (size_t)d0 * n + c, (size_t)n,
@@ -69,17 +76,10 @@ static int run_cells_pair(const G &g, int n, int nisurf, int grow_on, int year0,
         first = code;
         break;
       }
-      for (int r = 0; r < 12 + L; r++) ann[((size_t)y * (12 + L) + r) * n + c] = a[r];
+      for (int r = 0; r < Rows<L>::ANNUAL; r++) ann[((size_t)y * Rows<L>::ANNUAL + r) * n + c] = a[r];
       d0 += nt;
     }
-    for (int i = 1; i <= L; i++) {
-      st[0 * n * L + c * L + i - 1] = s.h2o[i];
-      st[2 * n * L + c * L + i - 1] = s.smp[i];
-      if (grow_on) st[3 * n * L + c * (L + 1) + i - 1] = cs.lay(PF_ROOTR, i);
-    }
-    if (grow_on) st[3 * n * L + c * (L + 1) + L] = 0.0f;
-    q[c] = s.zwt; q[n + c] = s.wa; q[2 * n + c] = s.LAI; q[3 * n + c] = s.LAI_litter;
-    q[4 * n + c] = s.pm; q[5 * n + c] = s.pfm; q[6 * n + c] = s.plen; q[7 * n + c] = s.rdepth;
+    H9K_STORE_CELL(L, s, cs, rows.st.data(), n, c, grow_on, SC_N)
   }
   return first;
 }
@@ -109,40 +109,26 @@ static int run_site_cells(const G &g, int n, int nday, int nisurf, const float *
                           const float *daily, const float *lai, float *st, float *out, int *err) {
   const h9m::Tabs T = {E2, L2};
   int first = 0;
+  CellRows<L> rows(n, par, st);
 #pragma omp parallel for schedule(dynamic, 1)
   for (int c = 0; c < n; c++) {
     float store[FlatStore<L>::N], zt[zt_size<L>()];
     fill_zt<L>(g, zt);
     FlatStore<L> cs{store, zt};
     St<L> s;
-    for (int i = 1; i <= L; i++) {
-      cs.set_lay(PF_TS, i, par[0 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_HKS, i, par[1 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_BSW, i, par[2 * n * L + c * L + i - 1]);
-      cs.set_lay(PF_PSI, i, par[3 * n * L + c * L + i - 1]);
-      s.h2o[i] = st[0 * n * L + c * L + i - 1];
-      s.smp[i] = st[2 * n * L + c * L + i - 1];
-      cs.set_lay(PF_ROOTR, i, st[3 * n * L + c * (L + 1) + i - 1]);
-    }
-    cs.set_sc(PS_FMAX, par[4 * n * L + c]);
+    H9K_LOAD_LANE(L, cs, s, rows.par.data(), n, c, rows.st.data(), n, c)
+    H9K_LOAD_SCALARS(L, s, rows.st.data(), n, c)
     cell_inv_pair<L, G>(g, cs);
-    float *q = st + (size_t)n * (4 * L + 1);
-    s.zwt = q[c]; s.wa = q[n + c]; s.LAI = q[2 * n + c]; s.LAI_litter = q[3 * n + c];
-    s.pm = q[4 * n + c]; s.pfm = q[5 * n + c]; s.plen = q[6 * n + c]; s.rdepth = q[7 * n + c];
     int eday = 0, estep = 0;
     float ev = 0;
-    const int code = cell_site<L, G>(g, cs, s, st[1 * n * L + c * L], sub + c, daily + c, lai + c, out + c,
+    const int code = cell_site<L, G>(g, cs, s, rows.st[(size_t)Rows<L>::H2O_MA * n + c], sub + c, daily + c, lai + c, out + c,
                                      (size_t)n, nday, nisurf, eday, estep, ev, T);
     if (code) {
       err[4 * c] = code; err[4 * c + 1] = 0; err[4 * c + 2] = eday; err[4 * c + 3] = estep;
 #pragma omp atomic write
       first = code;
     }
-    for (int i = 1; i <= L; i++) {
-      st[0 * n * L + c * L + i - 1] = s.h2o[i];
-      st[2 * n * L + c * L + i - 1] = s.smp[i];
-    }
-    q[c] = s.zwt; q[n + c] = s.wa; q[2 * n + c] = s.LAI; q[3 * n + c] = s.LAI_litter;
+    H9K_STORE_CELL(L, s, cs, rows.st.data(), n, c, false, SC_SITE)
   }
   return first;
 }
