@@ -108,8 +108,13 @@ static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_
 #define H9G_SPARE_L10 0   // spare lanes in the 3-wave L = 10 build too (PairStore::kSpare)
 #endif
 
+// The one-column wave's task lanes (hydrology_pair kTask), a sum of
+//   1  its powers as two task rounds, a power per lane (rounds A and B, round 7)
+//   2  round C: the tridiagonal system's interface fluxes, a lane per interface
+//   4  the forward sweep's quotients by mk_div from one refined reciprocal per row
+// 2 and 4 need 1; 0 compiles the wave as the 11- and 22-column kernels' helper rounds.
 #ifndef H9G_P1_TASKS
-#define H9G_P1_TASKS 1   // the one-column wave's powers as two task rounds, a power per lane (hydrology_pair)
+#define H9G_P1_TASKS 7
 #endif
 
 template <int K>
@@ -1036,6 +1041,12 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   FV<1> p0{{zero}}, p1{{zero}};               // lane 0's and lane 1's power
   FV<2> eA{{zero, zero}}, eS{{zero, zero}};
   bool picks = true, aq_task = false;
+  // the interface fluxes (below); a one-column wave's round C evaluates them on
+  // the task lanes and sets flux_done, with the recharge section's smp, zq of
+  // layer max(jwt, 1) in rc_smp, rc_zq
+  float c_q[L + 1], c_1[L + 1], c_2[L + 1];
+  bool flux_done = false;
+  float rc_smp = zero, rc_zq = zero;
   {
     float *const outq[1] = {zq};
     float *const outk[4] = {hk, dhkdw, smp, dsmpdw};
@@ -1265,6 +1276,19 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       static_assert(NA <= 64 && CS::kRecip && CS::kRts && CS::kRtsHK, "a lane per task, every reciprocal stored");
       const bool st = sp.spare;
       const int hh = sp.h;
+#if (H9G_P1_TASKS & 2)
+      // round C's divisor of this lane's interface, zc(i+1) - zc(i), and its
+      // reciprocal: three registers kept over the year
+      float den_l = g.den(1);
+      double rden_l = g.rden(1);
+#pragma unroll
+      for (int i = 2; i <= L - 1; i++)
+        if ((sp.ln >> 2) + 1 == i) {
+          den_l = g.den(i);
+          rden_l = g.rden(i);
+        }
+      float c_qo, c_d1, c_d2;
+#endif
       int ln = sp.ln;
       opaque(ln);                          // the task decode recomputed here, not kept as lane masks over the year
       if (!st) {
@@ -1378,31 +1402,96 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       float o_dz = zero;
       if (aqu) o_dz = -bsw_a * o_z / (x_b * ts_a);            // dsmpdw1, on kind 5
       const uint64_t fl_b = lane_mask((m.div_bad(q_b) | sw_b) && (ka == 1 || (ka >= 4 && aqu)));
-      // ---- every layer's results, from the lanes that hold them (the index
-      // kept in a VGPR: the values stay out of the scalar registers)
-      int vz = 0;
-      opaque(vz);
-#pragma unroll
-      for (int i = 1; i <= L; i++) {
-        const int lb = 4 * (i - 1);
-        zq[i] = lane_get(o_z, vz + lb + 1);
-        hk[i] = lane_get(o_hk, vz + lb + 2);
-        dhkdw[i] = lane_get(o_dhk, vz + lb + 2);
-        smp[i] = lane_get(o_sm, vz + lb + 3);
-        dsmpdw[i] = lane_get(o_ds, vz + lb + 3);
-      }
-      p0.v[0] = lane_get(w_a, vz + 4 * L);
-      p1.v[0] = lane_get(w_a, vz + 4 * L + 1);
-      if (aqu) {
-        eA.v[0] = lane_get(o_z, vz + 4 * L);
-        eS.v[0] = lane_get(o_z, vz + 4 * L + 1);
-        eS.v[1] = lane_get(o_dz, vz + 4 * L + 1);
-      }
-      if (st) return 0;                    // the helper lanes' part ends here
       // ---- flags (wave-uniform): the pair lanes' exact re-runs
       constexpr uint64_t ALL_A = (1ull << (4 * L)) - 1;
       const bool bad_eq = (((fl_a & 0x3333333333333333ull) | (fl_b & 0x2222222222222222ull)) & ALL_A) != 0;
       const bool bad_hk = (fl_a & 0xCCCCCCCCCCCCCCCCull & ALL_A) != 0;
+      const bool bad_pk = ((fl_a >> (4 * L)) & 3) != 0 || (aqu && ((fl_b >> (4 * L)) & 3) != 0);
+      int vz = 0;
+      opaque(vz);
+      bool slow = true;                    // the pair lanes evaluate the fluxes themselves
+#if (H9G_P1_TASKS & 2)
+      // ---- round C: the tridiagonal's interface fluxes (flux3_f below, the
+      // same expressions on the same operands), interface i on the kind-2 lane
+      // of layer i, which holds hk(i), dhkdw(i): smp, dsmpdw of layers i and
+      // i+1 from their kind-3 lanes, zq of both from their kind-1 lanes.  The
+      // aquifer interface (i = L, read only when aqu) takes smp1, dsmpdw1
+      // from lane 4L+1 and zq(L+1) from lane 4L.
+      {
+        const bool top = ia == L;
+        const float n_sm = ka == 5 ? o_z : o_sm, n_ds = ka == 5 ? o_dz : o_ds;
+        const int sn = top ? 4 * L + 1 : ln + 5, zn = top ? 4 * L : ln + 3;
+        const float sm_i = lane_get(o_sm, (ln + 1) & 63), ds_i = lane_get(o_ds, (ln + 1) & 63);
+        const float sm_n = lane_get(n_sm, sn & 63), ds_n = lane_get(n_ds, sn & 63);
+        const float zq_i = lane_get(o_z, (ln + 63) & 63), zq_n = lane_get(o_z, zn & 63);
+        float den_c = den_l;
+        double rden_c = rden_l;
+        if (aqu) {
+          const float zcA_c = 0.5f * (zw + g.zc(L));
+          const float dA = zcA_c - g.zc(L);
+          const double rA = recip64(dA);
+          den_c = top ? dA : den_c;
+          rden_c = top ? rA : rden_c;
+        }
+        const float num = (sm_n - sm_i) - (zq_n - zq_i);
+        c_qo = m.div_d(-o_hk * num, den_c, rden_c);
+        c_d1 = m.div_d(-(-o_hk * ds_i + num * o_dhk), den_c, rden_c);
+        c_d2 = m.div_d(-(o_hk * ds_n + num * o_dhk), den_c, rden_c);
+        bool f_c = (m.div_bad(c_qo) | m.div_bad(c_d1) | m.div_bad(c_d2)) && ka == 2 && (!top || aqu);
+#if defined(H9G_FORCE_RERUN)   // test builds: the pair lanes' flux block in about one wave-substep of two
+        f_c |= (__builtin_bit_cast(uint32_t, zw) & 1u) == 0;
+#endif
+        slow = bad_eq | bad_hk | bad_pk | (lane_mask(f_c) != 0);
+      }
+      // ---- the pair lanes read every interface's fluxes and every layer's
+      // smp (the state, and the next substep's beta), from the lanes that hold
+      // them (the index kept in a VGPR: the values stay out of the scalar
+      // registers); the recharge section's smp, zq of layer max(jwt, 1)
+#pragma unroll
+      for (int i = 1; i <= L; i++) {
+        const int lb = 4 * (i - 1);
+        smp[i] = lane_get(o_sm, vz + lb + 3);
+        if (i < L) {
+          c_q[i] = lane_get(c_qo, vz + lb + 2);
+          c_1[i] = lane_get(c_d1, vz + lb + 2);
+          c_2[i] = lane_get(c_d2, vz + lb + 2);
+        }
+      }
+      c_q[L] = c_1[L] = c_2[L] = zero;
+      if (aqu) {
+        c_q[L] = lane_get(c_qo, vz + 4 * L - 2);
+        c_1[L] = lane_get(c_d1, vz + 4 * L - 2);
+        c_2[L] = lane_get(c_d2, vz + 4 * L - 2);
+      }
+      {
+        const int lm = 4 * ((jwu > 1 ? jwu : 1) - 1);
+        rc_smp = lane_get(o_sm, vz + lm + 3);
+        rc_zq = lane_get(o_z, vz + lm + 1);
+      }
+#endif
+      p0.v[0] = lane_get(w_a, vz + 4 * L);
+      p1.v[0] = lane_get(w_a, vz + 4 * L + 1);
+      // ---- a flagged wave-substep: every layer's results to the pair lanes,
+      // which run their own flux block below (a uniform branch, all lanes
+      // still here)
+      if (__builtin_expect(slow, 0)) {
+#pragma unroll
+        for (int i = 1; i <= L; i++) {
+          const int lb = 4 * (i - 1);
+          zq[i] = lane_get(o_z, vz + lb + 1);
+          hk[i] = lane_get(o_hk, vz + lb + 2);
+          dhkdw[i] = lane_get(o_dhk, vz + lb + 2);
+          smp[i] = lane_get(o_sm, vz + lb + 3);
+          dsmpdw[i] = lane_get(o_ds, vz + lb + 3);
+        }
+        if (aqu) {
+          eA.v[0] = lane_get(o_z, vz + 4 * L);
+          eS.v[0] = lane_get(o_z, vz + 4 * L + 1);
+          eS.v[1] = lane_get(o_dz, vz + 4 * L + 1);
+        }
+      }
+      if (st) return 0;                    // the helper lanes' part ends here
+      flux_done = !slow;
       if (__builtin_expect(bad_eq, 0)) {
 #pragma unroll
         for (int t = 0; t < NT; t++) {
@@ -1418,8 +1507,15 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           for (int kk = 0; kk < 4; kk++) sp.xchg(r.v[kk], outk[kk][2 * t + 1], outk[kk][2 * t + 2]);
         }
       }
+#if (H9G_P1_TASKS & 2)
+      if (__builtin_expect(slow, 0)) {     // the recharge section's operands from the (exact) arrays
+#pragma unroll
+        for (int i = 1; i <= L; i++)
+          if (i == (jwt > 1 ? jwt : 1)) { rc_smp = smp[i]; rc_zq = zq[i]; }
+      }
+#endif
       aq_task = aqu;
-      picks = ((fl_a >> (4 * L)) & 3) != 0 || (aqu && ((fl_b >> (4 * L)) & 3) != 0);
+      picks = bad_pk;
     } else if constexpr (SP::kSpare && CS::kSpare && !M::kExact) {
       // Helper lanes (round 4: "spare lanes"; round 5: any number of slots).
       // A wave's C pairs use S = 2C of its 64 lanes; the other H = 64 - S
@@ -1735,6 +1831,15 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       d2[k] = m.div_d(-(hki * dsn + num * dhk), den, rden);
       b |= m.div_bad(qo[k]) | m.div_bad(d1[k]) | m.div_bad(d2[k]);
     };
+    if constexpr (kTask && (H9G_P1_TASKS & 2)) {   // a one-column wave: round C's, unless a flag sent it here
+#pragma unroll
+      for (int i = 1; i <= L; i++) {
+        qo[i] = c_q[i];
+        d1[i] = c_1[i];
+        d2[i] = c_2[i];
+      }
+    }
+    if (!kTask || __builtin_expect(!flux_done, 0)) {
 #pragma unroll
     for (int i = 1; i <= L - 1; i++)
       flux3_f(hk[i], (smp[i + 1] - smp[i]) - (zq[i + 1] - zq[i]), dsmpdw[i], dsmpdw[i + 1], dhkdw[i], g.den(i),
@@ -1761,6 +1866,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       }
       bad = false;
     }
+    }  // !flux_done
     auto row_f = [&](int i, float am, float bm, float cm, float rm) __attribute__((always_inline)) {
       float x;
       if (i == 1) {
@@ -1771,12 +1877,22 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
         zp |= BET == 0.0f;
         x = rm - am * dwat2[i - 1];
       }
+      if constexpr (kTask && (H9G_P1_TASKS & 4)) {
+        // a lone wave waits on every row's chain: both quotients by Markstein's
+        // correction from one refined reciprocal of BET (mk_div), six dependent
+        // f32 operations for recip64's and div_d's eight in f64.  The +0
+        // operands of rows L and L+1 with the water table in the column pass
+        // (mk_div_z); a range flag re-runs the exact sweep like div_bad.
+        dwat2[i] = i == L + 1 ? mk_div_z(x, BET, bad) : mk_div(x, BET, bad);
+        if (i <= L) GAM[i + 1] = i == L ? mk_div_z(cm, BET, bad) : mk_div(cm, BET, bad);
+      } else {
       const double rb = recip64(BET);
       dwat2[i] = m.div_d(x, BET, rb);
       bad |= m.div_bad(dwat2[i]);
       if (i <= L) {
         GAM[i + 1] = m.div_d(cm, BET, rb);
         bad |= m.div_bad(GAM[i + 1]);
+      }
       }
     };
     auto dzdt = [&](float dz) __attribute__((always_inline)) {
@@ -1907,10 +2023,18 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     const int j1 = jwt + 1;
     const float hks_j = cs.lay(PF_HKS, j1);
     float smp_m = zero, zq_m = zero, zc_j = zero;
+    if constexpr (kTask && (H9G_P1_TASKS & 2)) {   // from round C's lane reads (or its fallback)
+      smp_m = rc_smp;
+      zq_m = rc_zq;
+#pragma unroll
+      for (int i = 1; i <= L; i++)
+        if (i == jwt) zc_j = g.zc(i);
+    } else {
 #pragma unroll
     for (int i = 1; i <= L; i++) {
       if (i == (jwt > 1 ? jwt : 1)) { smp_m = smp[i]; zq_m = zq[i]; }
       if (i == jwt) zc_j = g.zc(i);
+    }
     }
     const float wh_zwt = zero;
     // the two powers came from the first round above (p0, p1)

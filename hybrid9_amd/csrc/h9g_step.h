@@ -190,6 +190,17 @@ H9K_HD float mk_div(float x, float d, bool &bad) {
   bad |= (ux > ud ? ux : ud) >= 0x5d800000u - 0x21800000u;                             // 2^60
   return q;
 }
+// The same, with x = +0 in range too: q0 = RN(+0 * y) is the zero of d's
+// sign, the residual fma(-d, q0, +0) is +0, and fma(+0, y, q0) = q0, the
+// IEEE quotient.  (x = -0 stays flagged: its residual is +0 as well, and
+// fma(+0, y, q0) then loses the sign where d > 0.)
+H9K_HD float mk_div_z(float x, float d, bool &bad) {
+  bool b = false;
+  const float q = mk_div(x, d, b);
+  const uint32_t ud = (__builtin_bit_cast(uint32_t, d) & 0x7fffffffu) - 0x21800000u;
+  bad |= __builtin_bit_cast(uint32_t, x) == 0u ? ud >= 0x5d800000u - 0x21800000u : b;
+  return q;
+}
 
 // Reciprocal of a float divisor in double, |r - 1/d| <= 1.2 * 2^-53 |1/d|:
 // hardware estimate + two Newton steps (each squares the error and adds
