@@ -19,7 +19,8 @@ SRC = HERE / "csrc" / "h9g.hip"
 SRC_IO = HERE / "csrc" / "h9g_io.cpp"       # host-only NetCDF I/O
 DEPS = [SRC, SRC_IO, HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
         HERE / "csrc" / "h9g_synth.h", HERE / "csrc" / "h9g_geo.h",
-        HERE / "csrc" / "h9g_pair.h", HERE / "csrc" / "h9g_rows.h", HERE / "csrc" / "h9g_io.h",
+        HERE / "csrc" / "h9g_pair.h", HERE / "csrc" / "h9g_expr.h", HERE / "csrc" / "h9g_rows.h",
+        HERE / "csrc" / "h9g_io.h",
         HERE.parent / "include" / "h9g.h"]
 OUT = HERE / "lib" / "libh9g.so"
 ARCH = os.environ.get("H9G_ARCH", "gfx950")

@@ -28,6 +28,7 @@
 // interleaved over its two columns) and FlatStore (host, flat per cell).
 #pragma once
 #include "h9g_step.h"
+#include "h9g_expr.h"
 #if !defined(__HIPCC__) && !defined(__HIP__)
 #define __device__
 #define __forceinline__ inline
@@ -72,42 +73,9 @@ static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_
                   (PS_DAY + D_DRR) % 2 == 0 && (PS_DAY + D_RAC) % 2 == 0 && PS_DR0 % 2 == 0,
               "pair fields must start a row");
 
-#ifndef H9G_FE_EQ
-#define H9G_FE_EQ 1   // fence interval of the equilibrium-profile slots (Split2::par)
-#endif
-#ifndef H9G_FE_HK
-#define H9G_FE_HK 1   // ... of the conductivity / matric-potential slots
-#endif
-#ifndef H9G_FE2
-#define H9G_FE2 1     // both, in the 2-wave build (PairStore R = 2)
-#endif
-#ifndef H9G_SPARE_FENCE
-#define H9G_SPARE_FENCE 0      // rounds of the spare-lane phases followed by a scheduling fence (bit q)
-#endif
-#ifndef H9G_INL_LAST
-// the in-layer case branch-free in the pairs' last-slot round (hydrology_pair;
-// round 5: 182.7 -> 181.8 ms, three alternating pairs on one box)
-#define H9G_INL_LAST 1
-#endif
 #ifndef H9G_EB_FAST
-#define H9G_EB_FAST 1    // round 5: 182.2 -> 181.7 ms; the energy balance's quotients branch-free, runtime divisors by Markstein (hydrology_pair)
+#define H9G_EB_FAST 1    // round 5: 182.2 -> 181.7 ms; the energy balance's quotients branch-free, runtime divisors by Markstein (hydrology_pair); 0: the exact block alone (tests)
 #endif
-#ifndef H9G_HK_MDIV
-#define H9G_HK_MDIV 1    // the conductivity phase's dsmpdw quotient by Markstein at L = 8 (hk_body; round 5: -0.3%; L = 10: +0.8%)
-#endif
-#ifndef H9G_INL_MDIV
-#define H9G_INL_MDIV 0   // the in-layer case's PTE / (zw - zlo) by Markstein (eq_body) instead of recip64
-#endif
-#ifndef H9G_WT_DEFER
-#define H9G_WT_DEFER 1   // the water-table loops' x/1000 flag the substep's exact re-run (hydrology_pair; round 5: -0.45%)
-#endif
-#ifndef H9G_AQ_FREE
-#define H9G_AQ_FREE 0    // the aquifer node's second round and interface branch-free (hydrology_pair)
-#endif
-#ifndef H9G_SPARE_L10
-#define H9G_SPARE_L10 0   // spare lanes in the 3-wave L = 10 build too (PairStore::kSpare)
-#endif
-
 // The one-column wave's task lanes (hydrology_pair kTask), a sum of
 //   1  its powers as two task rounds, a power per lane (rounds A and B, round 7)
 //   2  round C: the tridiagonal system's interface fluxes, a lane per interface
@@ -211,7 +179,6 @@ H9K_HD float hi_d(double v) {
 template <int L>
 struct FlatStore {                     // host: one flat array per cell
   static constexpr bool kRecip = true, kRts = true, kDayRecip = true, kRtsHK = true, kSpare = false;
-  static constexpr int FE_EQ = 1, FE_HK = 1;
   static constexpr int N = PF_N * L + PS_N;
   float *b;
   const float *zt;                     // zi(0..L+1), then zi(0..L+1)/1000
@@ -365,17 +332,13 @@ struct PairStore {
   const lds_float *zt;                 // zi(0..L+1), then zi(0..L+1)/1000 (per block)
   float *svw;                          // this workgroup's day-snapshot block (global)
   static constexpr int RESIDENT = R;                        // workgroups per CU = waves per SIMD
-  // fence intervals of the per-layer phases' slots (Split2::par_d): one slot
-  // per scheduling region at 3 waves per SIMD (wider regions spill, DESIGN.md
-  // §3); the 2-wave build has the registers for H9G_FE2 slots per region
-  static constexpr int FE_EQ = R <= 2 ? H9G_FE2 : H9G_FE_EQ, FE_HK = R <= 2 ? H9G_FE2 : H9G_FE_HK;
   Pacer pace;
   lds_float *wb;                       // the wave's block (column 0): spare lanes' stolen slots
   static constexpr int LANES = S;
   // helper lanes in the per-layer phases (hydrology_pair): not in the 3-wave
   // L = 10 build of 22-column waves, whose registers they push further into
   // scratch
-  static constexpr bool kSpare = H9G_SPARE_L10 || !(L >= 10 && R >= 3 && S >= 44);
+  static constexpr bool kSpare = !(L >= 10 && R >= 3 && S >= 44);
   __device__ __forceinline__ void day_start(int day) const { pace.day_start(day, RESIDENT); }
   __device__ __forceinline__ float zi(int i) const { return zt[i]; }
   __device__ __forceinline__ float zim(int i) const { return zt[L + 2 + i]; }
@@ -452,7 +415,6 @@ struct PairStore {
 template <int L>
 struct SoloStore {
   static constexpr bool kRecip = false, kRts = false, kDayRecip = false, kRtsHK = false, kSpare = false;
-  static constexpr int FE_EQ = 1, FE_HK = 1;
   static constexpr int NPF = PF_RPSI0 + 2;           // TS..ROOTR, SVH2O, SVSMP
   static constexpr int NPS = PS_LAI + 5;             // FMAX..DAY, SV*
   static constexpr int ROWS = NPF * L + NPS;
@@ -549,23 +511,10 @@ struct SplitAll {
   H9K_HD SplitAll fresh() const { return *this; }
   template <class CS>
   H9K_HD float own(const CS &cs, int p, int t, int h) const { return cs.lay(p, 2 * t + 1 + h); }
-  // out[2t+1+h] = f(t, h).f for every layer; K outputs per layer
-  template <int NT, int K, int FE = 1, class F>
-  H9K_HD void par(F f, float *const (&out)[K]) const {
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const FV<K> r = f(t, h);
-#pragma unroll
-        for (int k = 0; k < K; k++) out[k][2 * t + 1 + h] = r.v[k];
-      }
-      sched_fence();
-    }
-  }
-  // par with deferred checks: fast(t, h, bad) is branch-free and sets bad
-  // when any of its results needs glibc's/IEEE's other path; exact(t, h)
-  // (the body with in-place redos) then recomputes the layer.
+  // out[2t+1+h] = fast(t, h, bad) for every layer, K outputs per layer:
+  // fast is branch-free and sets bad when any of its results needs
+  // glibc's/IEEE's other path; exact(t, h) (the body with in-place redos)
+  // then recomputes the layer.
   template <int NT, int K, int FE = 1, class FF, class FX>
   H9K_HD void par_d(FF fast, FX exact, float *const (&out)[K]) const {
 #pragma unroll
@@ -619,22 +568,11 @@ struct Split2 {
   }
   template <class CS>
   H9K_HD float own(const CS &cs, int p, int t, int) const { return cs.slot(p, t); }
-  // FE: a scheduling fence after every FE slots (FE > 1 lets the scheduler
-  // interleave FE slots' powers, at FE times the live temporaries)
-  template <int NT, int K, int FE = 1, class F>
-  H9K_HD void par(F f, float *const (&out)[K]) const {
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      const FV<K> r = f(t, h);
-#pragma unroll
-      for (int k = 0; k < K; k++) xchg(r.v[k], out[k][2 * t + 1], out[k][2 * t + 2]);
-      if ((t + 1) % FE == 0 || t == NT - 1) sched_fence();
-    }
-  }
-  // par with the special-case checks of all NT slots deferred to one
-  // rarely-taken branch after them (SplitAll::par_d): with no per-slot
-  // branch the slots form one basic block, so the scheduler can interleave
-  // FE slots' powers.  A lane with any flag recomputes its slots exactly.
+  // The special-case checks of all NT slots deferred to one rarely-taken
+  // branch after them (SplitAll::par_d).  A lane with any flag recomputes its
+  // slots exactly.  A scheduling fence follows every FE slots: one slot per
+  // region for the powers (wider regions spill); FE = NT for
+  // slots without powers (beta), which the scheduler may interleave.
   template <int NT, int K, int FE = 1, class FF, class FX>
   H9K_HD void par_d(FF fast, FX exact, float *const (&out)[K]) const {
     FV<K> r[NT];
@@ -897,7 +835,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   const float Ra = DC(D_DG) * DC(D_RAA);
   float rsc, tran, evg;
   bool eb_fast = false;
-  if constexpr (H9G_EB_FAST && !M::kExact && (CS::kDayRecip || H9G_EB_FAST >= 2)) {
+  if constexpr (H9G_EB_FAST && !M::kExact && CS::kDayRecip) {
     // The energy balance's chain of quotients (:283-389) branch-free: the
     // day constants' by their stored double reciprocals (MathFast::div_d),
     // the runtime divisors by mk_div (Markstein's correction of the refined
@@ -907,13 +845,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     bool bad = false;
     auto mdiv = [&](float x, float d) __attribute__((always_inline)) { return mk_div(x, d, bad); };
     auto ddiv = [&](float x, float d, auto rget) __attribute__((always_inline)) {
-      if constexpr (CS::kDayRecip) {   // the store has the day constants' double reciprocals
-        const float q = m.div_d(x, d, rget());
-        bad |= m.div_bad(q);
-        return q;
-      } else {
-        return mdiv(x, d);
-      }
+      const float q = m.div_d(x, d, rget());   // the store has the day constants' double reciprocals
+      bad |= m.div_bad(q);
+      return q;
     };
     // :283-295
     const bool open = (DC(D_OK) != zero) && (beta > zero);
@@ -1093,15 +1027,11 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
               vol_eq = MINF(ts, vol_eq);
               vol_eq = MAXF(vol_eq, zero);
             } else {
-              const float tempi = tpi;
-              vol_eq = OWN(PF_C3) * (tempi - temp0);
-              vol_eq = MAXF(vol_eq, 0.0f);
-              vol_eq = MINF(ts, vol_eq);
+              vol_eq = vol_eq_below(OWN(PF_C3), ts, tpi, temp0);
             }
           }
           const float qv = divr<CS::kRts>(m, vol_eq, ts, [&]() { return join_d(OWN(PF_RTS0), OWN(PF_RTS1)); });
-          float z = psi * m.powf(MAXX(qv, 0.01f), -OWN(PF_BSW));
-          return FV<1>{{MAXC(smpmin, z)}};
+          return FV<1>{{smp_of(psi, m.powf(MAXX(qv, 0.01f), -OWN(PF_BSW)))}};
     };
     // fast: the same values branch-free (all three cases evaluated, the
     // layer's selected); bad = some quotient or power of the selected case
@@ -1111,7 +1041,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     // water table (mm): a lane's own slot (eq_fast) or, on a spare lane,
     // another pair's last slot (below).
     // inl_all: evaluate the in-layer case for every lane, branch-free (the
-    // round where the pairs evaluate their last slot, H9G_INL_LAST)
+    // round where the pairs evaluate their last slot: round 5, 182.7 -> 181.8 ms)
     auto eq_body = [&](int il, auto O, float zw, bool &bad, bool inl_all) __attribute__((always_inline)) -> FV<1> {
           const float zlo = cs.zi(il - 1), zhi = cs.zi(il);
           const float ts = O(PF_TS), psi = O(PF_PSI);
@@ -1134,28 +1064,15 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           float vin = zero;
           if (inl_all || any_lane(inl)) {
           H9G_BR(BR_INL);
-          const float d0 = zw - zlo;
-#if H9G_INL_MDIV
-          bool bq = false;
-          const float q1 = mk_div(O(PF_PTE), d0, bq);
-#else
-          const float q1 = m.div_d(O(PF_PTE), d0, recip64(d0));
-          const bool bq = m.div_bad(q1);
-#endif
-          const float voleq1 = q1 * (one - temp0);
-          vin = m.div_d(voleq1 * (zw - zlo) + ts * (zhi - zw), zhi - zlo, cs.rdz_t(il));
-          bad |= inl && (bq | m.div_bad(vin));
-          vin = MINF(ts, vin);
-          vin = MAXF(vin, zero);
+          vin = vol_eq_in_fast(m, [&]() { return O(PF_PTE); }, ts, temp0, zw, zlo, zhi,
+                               [&]() { return cs.rdz_t(il); }, inl, bad);   // (round A below keeps a copy)
           }
           // water table below the layer (:548-558)
-          float vbl = O(PF_C3) * (tpi - temp0);
-          vbl = MAXF(vbl, 0.0f);
-          vbl = MINF(ts, vbl);
+          const float vbl = vol_eq_below(O(PF_C3), ts, tpi, temp0);
           const float vol_eq = sat ? ts : (inl ? vin : vbl);
           const float qv = divr_d<CS::kRts>(m, vol_eq, ts, [&]() { return join_d(O(PF_RTS0), O(PF_RTS1)); }, bad);
           bool sz;
-          const float z = psi * m.powf_d(MAXX(qv, 0.01f), -O(PF_BSW), sz);
+          const float z = psi * m.powf_d(MAXX(qv, 0.01f), -O(PF_BSW), sz);   // a copy of smp_of (h9g_expr.h)
           bad |= sz;
           return FV<1>{{MAXC(smpmin, z)}};
     };
@@ -1174,9 +1091,8 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           float s1 = 0.5f * (th + thp) / (0.5f * (ts + tsp));
           s1 = MINC(one, s1);
           const float bsw = OWN(PF_BSW);
-          float s_node = MAXX(divr<CS::kRtsHK>(m, th, ts, [&]() { return join_d(OWN(PF_RTS0), OWN(PF_RTS1)); }),
-                              0.01f);
-          s_node = MINC(one, s_node);
+          const float s_node =
+              sat_node(divr<CS::kRtsHK>(m, th, ts, [&]() { return join_d(OWN(PF_RTS0), OWN(PF_RTS1)); }));
           // the two powers are independent: one deferred check
           const float ek = 2.0f * bsw + 2.0f, es = -bsw;
           bool sk, ss;
@@ -1186,14 +1102,13 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
             m.powf_fix(pk, s1, ek, sk);
             m.powf_fix(ps, s_node, es, ss);
           }
-          const float s2 = OWN(PF_HKS) * pk;
+          const float s2 = OWN(PF_HKS) * pk;                  // a copy of hk_dhk (h9g_expr.h)
           FV<4> r;
           r.v[0] = s1 * s2;
           r.v[1] = (2.0f * bsw + 3.0f) * s2 * OWN(PF_ITS);
-          float sm = OWN(PF_PSI) * ps;
-          sm = MAXC(smpmin, sm);
+          const float sm = smp_of(OWN(PF_PSI), ps);
           r.v[2] = sm;
-          r.v[3] = (-bsw) * sm / (s_node * ts);
+          r.v[3] = dsmpdw_div(bsw, sm, s_node, ts);
           return r;
     };
     // the same, branch-free, flags deferred (par_d); hk_body as eq_body, with
@@ -1201,39 +1116,19 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     // most L) given
     auto hk_body = [&](auto O, float th, float thp, float tsp, bool &bad) __attribute__((always_inline)) -> FV<4> {
           const float ts = O(PF_TS);
-          // s1 = RN(0.5a / 0.5b) = RN(a / b) (the halvings are exact for
-          // normal a, b), from y = PF_ITS = RN(1/b) by Markstein's correction:
-          // q0 = RN(a y), e = a - b q0 (exact), RN(q0 + e y) = RN(a / b) when
-          // nothing under- or overflows.  a, b in [2^-60, 2^60) keeps q and e
-          // normal; other operands flag the slot for hk_exact.  (The IEEE
-          // division took 11 VALU in a chain of 9; tools/markstein_check.c.)
-          const float sa = th + thp, sb = ts + tsp, its = O(PF_ITS);
-          const float q0 = sa * its;
-          float s1 = __builtin_fmaf(__builtin_fmaf(-sb, q0, sa), its, q0);
-          const uint32_t ua = __builtin_bit_cast(uint32_t, sa) - 0x21800000u;   // 2^-60
-          const uint32_t ub = __builtin_bit_cast(uint32_t, sb) - 0x21800000u;
-          bad |= (ua > ub ? ua : ub) >= 0x5d800000u - 0x21800000u;             // 2^60
-          s1 = MINC(one, s1);
+          const float s1 = s1_mk(th + thp, ts + tsp, O(PF_ITS), bad);   // flagged for hk_exact
           const float bsw = O(PF_BSW);
-          float s_node = MAXX(divr_d<CS::kRtsHK>(m, th, ts, [&]() { return join_d(O(PF_RTS0), O(PF_RTS1)); }, bad),
-                              0.01f);
-          s_node = MINC(one, s_node);
+          const float s_node =
+              sat_node(divr_d<CS::kRtsHK>(m, th, ts, [&]() { return join_d(O(PF_RTS0), O(PF_RTS1)); }, bad));
           const float ek = 2.0f * bsw + 2.0f, es = -bsw;
           bool sk, ss;
           const float pk = m.powf_d(s1, ek, sk);
           const float ps = m.powf_d(s_node, es, ss);
           bad |= sk | ss;
-          const float s2 = O(PF_HKS) * pk;
           FV<4> r;
-          r.v[0] = s1 * s2;
-          r.v[1] = (2.0f * bsw + 3.0f) * s2 * O(PF_ITS);
-          float sm = O(PF_PSI) * ps;
-          sm = MAXC(smpmin, sm);
-          r.v[2] = sm;
-          if constexpr (H9G_HK_MDIV && L <= 8)
-            r.v[3] = mk_div((-bsw) * sm, s_node * ts, bad);   // dsmpdw, flagged for hk_exact
-          else
-            r.v[3] = (-bsw) * sm / (s_node * ts);
+          hk_dhk(s1, pk, O(PF_HKS), bsw, O(PF_ITS), r.v[0], r.v[1]);
+          r.v[2] = smp_of(O(PF_PSI), ps);
+          r.v[3] = dsmpdw_fast<L>(bsw, r.v[2], s_node, ts, bad);   // flagged for hk_exact
           return r;
     };
     auto hk_fast = [&](int t, int h, bool &bad) __attribute__((always_inline)) -> FV<4> {
@@ -1315,20 +1210,13 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       const double rts_a = join_d(oa[PF_RTS0 * L], oa[PF_RTS1 * L]);
       const float zlo_a = cs.zi(ia - 1), zhi_a = cs.zi(ia);
       const bool sat_a = zw <= zlo_a, inl_a = (zw < zhi_a) && (zw > zlo_a);
-      // s1 (hk_body: Markstein's correction from PF_ITS, range-flagged)
-      const float sa = th + thp, sb = ts_a + tsp_a;
-      const float q0 = sa * its_a;
-      float s1 = __builtin_fmaf(__builtin_fmaf(-sb, q0, sa), its_a, q0);
-      const uint32_t ua = __builtin_bit_cast(uint32_t, sa) - 0x21800000u;   // 2^-60
-      const uint32_t ub = __builtin_bit_cast(uint32_t, sb) - 0x21800000u;
-      const bool s1bad = (ua > ub ? ua : ub) >= 0x5d800000u - 0x21800000u;   // 2^60
-      s1 = MINC(one, s1);
+      bool s1bad = false;
+      const float s1 = s1_mk(th + thp, ts_a + tsp_a, its_a, s1bad);
       const bool by_ts = ka == 2 || ka == 3 || (ka == 4 && !aqu);            // theta / ts, else ... / -psi
       const float nz = (-psi_a + zw) - (ka == 0 ? zlo_a : zhi_a);
       const float num_a = by_ts ? th : (ka == 5 ? zw : nz);
       const float q_a = m.div_d(num_a, by_ts ? ts_a : -psi_a, by_ts ? rts_a : rpsi_a);
-      float sn_a = MAXX(q_a, 0.01f);
-      sn_a = MINC(one, sn_a);
+      const float sn_a = sat_node(q_a);
       const bool one_a = (ka == 0 && sat_a) || (ka == 1 && (sat_a || inl_a));
       const float x_a = ka == 2 ? s1 : (by_ts ? sn_a : (ka == 5 ? one + q_a : (one_a ? one : q_a)));
       const float e_a = (ka <= 1 || (ka == 4 && aqu)) ? one + ninv_a
@@ -1340,19 +1228,12 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       const float w_a = m.powf_d(x_a, e_a, sw_a);
       bool f_a = m.div_bad(q_a) | sw_a | (ka == 2 && s1bad);
       // ---- the rest of hk_body: kind 2 holds hk, dhkdw, kind 3 smp, dsmpdw
-      const float s2 = hks_a * w_a;
-      const float o_hk = x_a * s2;
-      const float o_dhk = (2.0f * bsw_a + 3.0f) * s2 * its_a;
-      float o_sm = psi_a * w_a;
-      o_sm = MAXC(smpmin, o_sm);
-      float o_ds;
-      if constexpr (H9G_HK_MDIV && L <= 8) {
-        bool b3 = false;
-        o_ds = mk_div((-bsw_a) * o_sm, x_a * ts_a, b3);
-        f_a |= ka == 3 && b3;
-      } else {
-        o_ds = (-bsw_a) * o_sm / (x_a * ts_a);
-      }
+      float o_hk, o_dhk;
+      hk_dhk(x_a, w_a, hks_a, bsw_a, its_a, o_hk, o_dhk);
+      const float o_sm = smp_of(psi_a, w_a);
+      bool b3 = false;
+      const float o_ds = dsmpdw_fast<L>(bsw_a, o_sm, x_a, ts_a, b3);
+      f_a |= ka == 3 && b3;
       // ---- the rest of eq_body up to vol_eq (:530-558), on kind 1: temp0 is
       // the even neighbour's power
       const float t0 = pair_bcast<0>(w_a);
@@ -1360,47 +1241,33 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       float vin = zero;
       if (any_lane(inl1)) {
         H9G_BR(BR_INL);
-        const float d0 = zw - zlo_a;
-#if H9G_INL_MDIV
-        bool bq = false;
-        const float q1 = mk_div(pte_a, d0, bq);
-#else
+        const float d0 = zw - zlo_a;             // a copy of vol_eq_in_fast (h9g_expr.h)
         const float q1 = m.div_d(pte_a, d0, recip64(d0));
         const bool bq = m.div_bad(q1);
-#endif
         const float voleq1 = q1 * (one - t0);
         vin = m.div_d(voleq1 * (zw - zlo_a) + ts_a * (zhi_a - zw), zhi_a - zlo_a, cs.rdz_t(ia));
         f_a |= inl1 && (bq | m.div_bad(vin));
         vin = MINF(ts_a, vin);
         vin = MAXF(vin, zero);
       }
-      float vbl = c3_a * (w_a - t0);
-      vbl = MAXF(vbl, 0.0f);
-      vbl = MINF(ts_a, vbl);
+      const float vbl = vol_eq_below(c3_a, ts_a, w_a, t0);
       const float vol_eq = sat_a ? ts_a : (inl_a ? vin : vbl);
       // ve of the aquifer node (:579-584), on kind 4 (its layer is L when aq)
       float ve = zero;
-      if (aqu) {
-        const float d0 = zw - g.zi(L);
-        ve = pte_a / d0 * (1.0f - w_a);
-        ve = MAXF(ve, 0.0f);
-        ve = MINF(ts_a, ve);
-      }
+      if (aqu) ve = vol_clamp(vol_aq(pte_a, zw - g.zi(L), w_a), ts_a);
       const uint64_t fl_a = lane_mask(f_a);
       pr.mark(2);
       // ---- round B
       const float num_b = ka == 4 ? ve : (ka == 5 ? th : vol_eq);
       const float q_b = m.div_d(num_b, ts_a, rts_a);
       const float xm_b = MAXX(q_b, 0.01f);
-      float sn_b = MAXX(0.5f * (one + q_b), 0.01f);
-      sn_b = MINC(one, sn_b);
+      const float sn_b = sat_node_aq(q_b);
       const float x_b = ka >= 4 ? (aqu ? (ka == 4 ? xm_b : sn_b) : one) : xm_b;
       bool sw_b;
       const float w_b = m.powf_d(x_b, -bsw_a, sw_b);
-      float o_z = psi_a * w_b;
-      o_z = MAXC(smpmin, o_z);
+      const float o_z = smp_of(psi_a, w_b);
       float o_dz = zero;
-      if (aqu) o_dz = -bsw_a * o_z / (x_b * ts_a);            // dsmpdw1, on kind 5
+      if (aqu) o_dz = dsmpdw_div(bsw_a, o_z, x_b, ts_a);      // dsmpdw1, on kind 5
       const uint64_t fl_b = lane_mask((m.div_bad(q_b) | sw_b) && (ka == 1 || (ka >= 4 && aqu)));
       // ---- flags (wave-uniform): the pair lanes' exact re-runs
       constexpr uint64_t ALL_A = (1ull << (4 * L)) - 1;
@@ -1433,10 +1300,10 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           den_c = top ? dA : den_c;
           rden_c = top ? rA : rden_c;
         }
-        const float num = (sm_n - sm_i) - (zq_n - zq_i);
-        c_qo = m.div_d(-o_hk * num, den_c, rden_c);
-        c_d1 = m.div_d(-(-o_hk * ds_i + num * o_dhk), den_c, rden_c);
-        c_d2 = m.div_d(-(o_hk * ds_n + num * o_dhk), den_c, rden_c);
+        const float num = flux_num(sm_n, sm_i, zq_n, zq_i);
+        c_qo = m.div_d(flux_q(o_hk, num), den_c, rden_c);
+        c_d1 = m.div_d(flux_d1(o_hk, num, ds_i, o_dhk), den_c, rden_c);
+        c_d2 = m.div_d(flux_d2(o_hk, num, ds_n, o_dhk), den_c, rden_c);
         bool f_c = (m.div_bad(c_qo) | m.div_bad(c_d1) | m.div_bad(c_d2)) && ka == 2 && (!top || aqu);
 #if defined(H9G_FORCE_RERUN)   // test builds: the pair lanes' flux block in about one wave-substep of two
         f_c |= (__builtin_bit_cast(uint32_t, zw) & 1u) == 0;
@@ -1590,10 +1457,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           bool b = false;
           r[t] = eq_body(st ? 2 * u + 1 + (k & 1) : 2 * t + 1 + hh,
                          [&](int p) __attribute__((always_inline)) { return o[p * NT * S]; },
-                         st ? zwk[q] : zwtmm, b, H9G_INL_LAST && U + q == NT - 1);
+                         st ? zwk[q] : zwtmm, b, U + q == NT - 1);
           rv[q] = r[t].v[0];
           fl |= (b ? 1 : 0) << q;
-          if ((H9G_SPARE_FENCE >> q) & 1) sched_fence();
         }
 #pragma unroll
         for (int u = 0; u < U; u++) r[u].v[0] = back(rv, u);
@@ -1651,7 +1517,6 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
 #pragma unroll
           for (int kk = 0; kk < 4; kk++) rv[kk][q] = r[t].v[kk];
           fl |= (b ? 1 : 0) << q;
-          if ((H9G_SPARE_FENCE >> q) & 1) sched_fence();
         }
 #pragma unroll
         for (int kk = 0; kk < 4; kk++)
@@ -1670,9 +1535,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     } else {
       // (round 3: the two phases' slots interleaved in one region, twice the
       // independent powers per region, spilled 225 VGPRs: 214.5 vs 208.9 ms)
-      sp.template par_d<NT, 1, CS::FE_EQ>(eq_fast, eq_exact, outq);
+      sp.template par_d<NT, 1>(eq_fast, eq_exact, outq);
       pr.mark(2);
-      sp.template par_d<NT, 4, CS::FE_HK>(hk_fast, hk_exact, outk);
+      sp.template par_d<NT, 4>(hk_fast, hk_exact, outk);
     }
   }
   if constexpr (SP::kSpare) {
@@ -1691,13 +1556,11 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // aquifer row, :581-590, :737-741) is read only by lanes below the column:
   // a wave with none skips it (wave-uniform); the deepening loop's rare
   // fall-through below the column evaluates s_y(L) itself for a lane inside.
-  // (H9G_AQ_FREE: evaluated by every wave; lanes inside the column take
-  // operands that make it an identity and raise no flag)
   bool any_aq_v;
   if constexpr (kTask)
     any_aq_v = aq_task;                       // one column: uniform
   else
-    any_aq_v = H9G_AQ_FREE || any_lane(aq);
+    any_aq_v = any_lane(aq);
   const bool any_aq = any_aq_v;
   if (!kTask || __builtin_expect(picks, 0)) {   // (a one-column wave: only when a task round flagged one of them)
   const int jc = aq ? L : jwt + 1;            // the layer whose -psi divides
@@ -1707,9 +1570,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
 #pragma unroll
     for (int i = 1; i <= L; i++)
       if (i == jc) th_j = theta[i];
-    const float s_node =
-        MAXX(divr<CS::kRts>(m, th_j, cs.lay(PF_TS, jc), [&]() { return lay_d(cs, PF_RTS0, jc); }), 0.01f);
-    s1c = MINC(one, s_node);
+    s1c = sat_node(divr<CS::kRts>(m, th_j, cs.lay(PF_TS, jc), [&]() { return lay_d(cs, PF_RTS0, jc); }));
     bsw_c = cs.lay(PF_BSW, jc);
   }
   sp.template pick<1>(
@@ -1734,9 +1595,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   H9G_BR(BR_ANYAQ);
   {
     const float d0 = aq ? (zwtmm - g.zi(L)) : one;
-    float ve = LAYF(PF_PTE, L) / d0 * (1.0f - pA.v[0]);
-    ve = MAXF(ve, 0.0f);
-    ve = MINF(TS(L), ve);
+    const float ve = vol_clamp(vol_aq(LAYF(PF_PTE, L), d0, pA.v[0]), TS(L));
     sp.template pick<2>(
         [&](int h) __attribute__((always_inline)) -> FV<2> {
           // the quotient's and the power's checks deferred to one branch
@@ -1744,8 +1603,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           // of the then out-of-line redo caused: DESIGN.md §3)
           const float xn = sel(h, ve, theta[L]);
           auto xof = [&](float q2) __attribute__((always_inline)) {
-            float sn = MAXX(0.5f * (one + q2), 0.01f);
-            sn = MINC(one, sn);
+            const float sn = sat_node_aq(q2);
             const float x = sel(h, MAXX(q2, 0.01f), sn);
             return aq ? x : one;
           };
@@ -1759,9 +1617,8 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
             x = xof(q2);
             pw = m.powf(x, -BSW(L));
           }
-          float z = PSI(L) * pw;
-          z = MAXC(smpmin, z);
-          return FV<2>{{z, -BSW(L) * z / (x * TS(L))}};
+          const float z = smp_of(PSI(L), pw);
+          return FV<2>{{z, dsmpdw_div(BSW(L), z, x, TS(L))}};
         },
         eA, eS);
   }
@@ -1794,9 +1651,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       BET = bm;
       x = rm;
     } else {
-      BET = bm - am * GAM[i];
+      BET = row_bet(am, bm, GAM[i]);
       if (BET == 0.0f && !zero_pivot) zero_pivot = i;
-      x = rm - am * dwat2[i - 1];
+      x = row_x(am, rm, dwat2[i - 1]);
     }
     rbet = recip64(BET);
     dwat2[i] = m.div_d(x, BET, rbet);
@@ -1826,9 +1683,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     float qo[L + 1], d1[L + 1], d2[L + 1];
     auto flux3_f = [&](float hki, float num, float dsi, float dsn, float dhk, float den, double rden, int k,
                        bool &b) __attribute__((always_inline)) {
-      qo[k] = m.div_d(-hki * num, den, rden);
-      d1[k] = m.div_d(-(-hki * dsi + num * dhk), den, rden);
-      d2[k] = m.div_d(-(hki * dsn + num * dhk), den, rden);
+      qo[k] = m.div_d(flux_q(hki, num), den, rden);
+      d1[k] = m.div_d(flux_d1(hki, num, dsi, dhk), den, rden);
+      d2[k] = m.div_d(flux_d2(hki, num, dsn, dhk), den, rden);
       b |= m.div_bad(qo[k]) | m.div_bad(d1[k]) | m.div_bad(d2[k]);
     };
     if constexpr (kTask && (H9G_P1_TASKS & 2)) {   // a one-column wave: round C's, unless a flag sent it here
@@ -1842,13 +1699,13 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     if (!kTask || __builtin_expect(!flux_done, 0)) {
 #pragma unroll
     for (int i = 1; i <= L - 1; i++)
-      flux3_f(hk[i], (smp[i + 1] - smp[i]) - (zq[i + 1] - zq[i]), dsmpdw[i], dsmpdw[i + 1], dhkdw[i], g.den(i),
+      flux3_f(hk[i], flux_num(smp[i + 1], smp[i], zq[i + 1], zq[i]), dsmpdw[i], dsmpdw[i + 1], dhkdw[i], g.den(i),
               g.rden(i), i, bad);
     qo[L] = d1[L] = d2[L] = zero;
     if (any_aq) {                      // aquifer interface (used when aq)
       const float den = zcA - g.zc(L);
       bool ba = false;
-      flux3_f(hk[L], smp1 - smp[L] - (zq[L + 1] - zq[L]), dsmpdw[L], dsmpdw1, dhkdw[L], den, recip64(den), L, ba);
+      flux3_f(hk[L], flux_num(smp1, smp[L], zq[L + 1], zq[L]), dsmpdw[L], dsmpdw1, dhkdw[L], den, recip64(den), L, ba);
       bad |= aq && ba;
     }
     // fluxes made exact here, so the layer arrays die before the sweep
@@ -1857,12 +1714,12 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
 #pragma unroll
       for (int i = 1; i <= L; i++) {
         const bool a = i == L;
-        const float num = a ? smp1 - smp[L] - (zq[L + 1] - zq[L]) : (smp[i + 1] - smp[i]) - (zq[i + 1] - zq[i]);
+        const float num = a ? flux_num(smp1, smp[L], zq[L + 1], zq[L]) : flux_num(smp[i + 1], smp[i], zq[i + 1], zq[i]);
         const float dsn = a ? dsmpdw1 : dsmpdw[i < L ? i + 1 : L];
         const float den = a ? zcA - g.zc(L) : g.den(i);
-        m.div_fix(qo[i], -hk[i] * num, den);
-        m.div_fix(d1[i], -(-hk[i] * dsmpdw[i] + num * dhkdw[i]), den);
-        m.div_fix(d2[i], -(hk[i] * dsn + num * dhkdw[i]), den);
+        m.div_fix(qo[i], flux_q(hk[i], num), den);
+        m.div_fix(d1[i], flux_d1(hk[i], num, dsmpdw[i], dhkdw[i]), den);
+        m.div_fix(d2[i], flux_d2(hk[i], num, dsn, dhkdw[i]), den);
       }
       bad = false;
     }
@@ -1873,9 +1730,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
         BET = bm;
         x = rm;
       } else {
-        BET = bm - am * GAM[i];
+        BET = row_bet(am, bm, GAM[i]);
         zp |= BET == 0.0f;
-        x = rm - am * dwat2[i - 1];
+        x = row_x(am, rm, dwat2[i - 1]);
       }
       if constexpr (kTask && (H9G_P1_TASKS & 4)) {
         // a lone wave waits on every row's chain: both quotients by Markstein's
@@ -1908,7 +1765,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     row_f(L, -d1[L - 1], dzdt(g.dz(L)) - d2[L - 1] + (aq ? d1[L] : zero), aq ? d2[L] : zero,
           qo[L - 1] - (aq ? qo[L] : zero) - tran * ROOT(L));
     const float qA = dzdt(dzA);
-    const float bmA = qA - d2[L] + zero;
+    const float bmA = qA - d2[L] + zero;   // (rows L, L+1: stated again by the exact sweep and the exact path)
     const float rmA = qo[L] - zero;
     row_f(L + 1, aq ? -d1[L] : zero, aq ? bmA : qA, zero, aq ? rmA : zero);
     if (__builtin_expect(bad | zp | (bm1 == 0.0f), 0)) {  // the exact sweep on the (exact) fluxes
@@ -1936,7 +1793,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // qout, dqodw1, dqodw2 of one interface: independent quotients, one check.
   auto flux3 = [&](float hki, float num, float dsi, float dsn, float dhk, float den, double rden, float &qo,
                    float &d1, float &d2) __attribute__((always_inline)) {
-    const float x0 = -hki * num, x1 = -(-hki * dsi + num * dhk), x2 = -(hki * dsn + num * dhk);
+    const float x0 = flux_q(hki, num), x1 = flux_d1(hki, num, dsi, dhk), x2 = flux_d2(hki, num, dsn, dhk);
     qo = m.div_d(x0, den, rden);
     d1 = m.div_d(x1, den, rden);
     d2 = m.div_d(x2, den, rden);
@@ -1950,6 +1807,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   {
     const float den = g.den(1);
     const double rden = g.rden(1);
+    // num, here and in the two blocks below: flux_num (h9g_expr.h) with dzq first, as the reference has it
     const float dzq = (zq[2] - zq[1]);
     const float num = (smp[2] - smp[1]) - dzq;
     float qout, dqodw1, dqodw2;
@@ -2059,9 +1917,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // x / 1000 in the water-table loops, which run only for a substep that
   // started with the water table in the column (a day snapshot exists): a
   // quotient that needs the IEEE division (subnormal) asks for the exact
-  // re-run of the substep instead of a redo branch in place (H9G_WT_DEFER)
+  // re-run of the substep instead of a redo branch in place (round 5: -0.45%)
   auto wdiv = [&](float x) __attribute__((always_inline)) {
-    if constexpr (H9G_WT_DEFER && !M::kExact) {
+    if constexpr (!M::kExact) {
       const float q = m.div_d(x, 1000.0f, r1000);
       m.special |= m.div_bad(q);
       return q;
