@@ -27,6 +27,7 @@ NFORCING = 7
 NANNUAL_SCALARS = 11
 NDIAG = 12
 NDAILY = 11              # H9G_NDAILY: the daily diagnostics line (site.DIAG_FIELDS)
+NMONTHS = 12             # H9G_NMONTHS
 ANNUAL_SCALARS = ("npp", "plant_mass", "rnf", "evap", "tas", "rlds", "rsds",
                   "huss", "ps", "pr", "rhs")
 DIAG_NAMES = ("cells", "rnf_sum", "theta_total_sum", "zwt_sum", "wa_sum",
@@ -131,6 +132,8 @@ def lib() -> C.CDLL:
                                      C.c_int, _FP, _FP]),
         "h9g_land_cells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, _I64P, _FP]),
         "h9g_write_axy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _I64P, _FP]),
+        "h9g_write_mxy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _I64P, C.c_int, C.c_int,
+                                       _FP]),
         "h9g_nc_forcing_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _I64P,
                                           C.c_int, C.c_int, _FP]),
         "h9g_nc_ntimes": (C.c_int, [C.c_char_p]),
@@ -145,6 +148,8 @@ def lib() -> C.CDLL:
         "h9g_run_site": (C.c_int, [vp, C.c_int, _FP, _FP, _FP, _FP]),
         "h9g_set_daily": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32)]),
         "h9g_get_daily": (C.c_int, [vp, C.c_int, _FP]),
+        "h9g_set_monthly": (C.c_int, [vp, C.c_int]),
+        "h9g_get_monthly": (C.c_int, [vp, C.c_int, _FP]),
         "h9g_host_expf": (C.c_float, [C.c_float]),
         "h9g_host_powf": (C.c_float, [C.c_float, C.c_float]),
     }
@@ -476,6 +481,28 @@ class Context:
         _check(rc, "h9g_get_daily")
         return out[:, :, :nsel]
 
+    # -- monthly output: month-end running sums ---------------------------
+    def set_monthly(self, on: bool = True):
+        """Turns monthly recording on or off (h9g_set_monthly; off by
+        default).  With it on, the next run_year, run_decade_ordered or
+        run_ordered runs the monthly year kernels, which also store the
+        year's 12+L running sums at every month end; annual means, state,
+        STOP records and daily lines are the same bit for bit either way."""
+        _check(self._lib.h9g_set_monthly(self._h, int(bool(on))), "h9g_set_monthly")
+
+    def get_monthly(self, k: int = 0) -> np.ndarray:
+        """The month-end snapshots of year k (0-based) of the last run_year
+        (k = 0) or ordered call: (12, 12+L, ncell) float32, the undivided
+        running sums in get_annual's row order (h9g_get_monthly; NaN for a
+        cell that stopped or is masked).  ``monthly_means`` derives the
+        months' means from them."""
+        out = np.empty((NMONTHS, 12 + self.L, self.ncell), dtype=np.float32)
+        rc = self._lib.h9g_get_monthly(self._h, int(k), _fp(out))
+        if rc == -4:
+            raise H9GError("h9g_get_monthly: nothing recorded (H9G_ESTATE): set_monthly(), then run")
+        _check(rc, "h9g_get_monthly")
+        return out
+
     def sync(self, raise_on_stop: bool = True) -> int:
         rc = _check(self._lib.h9g_sync(self._h), "h9g_sync")
         if rc and raise_on_stop:
@@ -589,6 +616,47 @@ def write_axy_nc(path, annual, gid, zc, nx: int = 720, ny: int = 360):
                                   gid.ctypes.data_as(_I64P), _fp(annual)), "h9g_write_axy_nc")
 
 
+def write_mxy_nc(path, snapshots, gid, zc, jyear: int, nisurf: int, nx: int = 720, ny: int = 360):
+    """One year of monthly means, derived as ``monthly_means`` derives them
+    from the month-end snapshots (12, 12+L, ncell) of the cells gid, to
+    mxyYYYY.nc: write_axy_nc's variables under a leading dimension month
+    (h9g_write_mxy_nc; netCDF classic)."""
+    snapshots = np.ascontiguousarray(snapshots, dtype=np.float32)
+    gid = np.ascontiguousarray(gid, dtype=np.int64)
+    zc = np.ascontiguousarray(zc, dtype=np.float32)
+    L = snapshots.shape[1] - 12
+    assert snapshots.shape == (NMONTHS, 12 + L, gid.size) and zc.size == L
+    _check(lib().h9g_write_mxy_nc(str(path).encode(), nx, ny, L, _fp(zc), gid.size, gid.ctypes.data_as(_I64P),
+                                  int(jyear), int(nisurf), _fp(snapshots)), "h9g_write_mxy_nc")
+
+
+def month_ends(jyear: int) -> np.ndarray:
+    """The last day (1-based) of each month of jyear, INIT.f90:844-859."""
+    e = np.array([31, 59, 90, 120, 151, 181, 212, 243, 273, 304, 334, 365])
+    if days_in_year(jyear) == 366:
+        e[1:] += 1
+    return e
+
+
+def monthly_means(snapshots, jyear: int, nisurf: int) -> np.ndarray:
+    """Monthly means from one year's month-end snapshots (12, 12+L, ncell)
+    (Context.get_monthly): in float64, (S[m] - S[m-1]) / days_m with
+    S[-1] = 0, rounded to float32; the divisor is days_m * nisurf for rnf
+    (row 2) and 1 for npp (row 0, a monthly total, as the annual row is a
+    yearly total).  Row evap (3) is the reference's zero.  Derived from the
+    reference's f32 running sums: deterministic, but not a reference
+    quantity (the reference writes annual means only)."""
+    s = np.asarray(snapshots, dtype=np.float32).astype(np.float64)
+    if s.ndim != 3 or s.shape[0] != NMONTHS:
+        raise ValueError("monthly_means: snapshots must be (12, 12+L, ncell)")
+    d = np.diff(s, axis=0, prepend=np.zeros_like(s[:1]))
+    days = np.diff(month_ends(jyear), prepend=0).astype(np.float64)
+    div = np.repeat(days[:, None], s.shape[1], axis=1)
+    div[:, 0] = 1.0
+    div[:, 2] = days * float(nisurf)
+    return (d / div[:, :, None]).astype(np.float32)
+
+
 def decades(year0: int, nyears: int):
     """The reference's decades (HYBRID9.f90:93-113: 1901-1910, 1911-1920,
     ...) cut to [year0, year0 + nyears): list of (first year, years)."""
@@ -601,7 +669,8 @@ def decades(year0: int, nyears: int):
 
 
 def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
-                   state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None):
+                   state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None,
+                   monthly=False):
     """``run`` in the reference's own cell order (smp carried from cell to
     cell, cells in the given order; chains: a reference rank per cell, each
     rank its own chain, shard.reference_blocks).  pipelined: one
@@ -611,7 +680,9 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
     err, errors, passes (per decade), work (decade_stats per call),
     overlap (ordered_stats, pipelined)).  daily_cells: the cells whose daily
     line is recorded (Context.set_daily) -> out["daily"] (ndays, 11, nsel); the
-    decades then run one after another."""
+    decades then run one after another.  monthly: the month-end snapshots
+    (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n); the decades
+    stay overlapped."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device,
@@ -620,6 +691,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
         ctx.set_params(params)
         if daily_cells is not None:
             ctx.set_daily(daily_cells)
+        if monthly:
+            ctx.set_monthly(True)
         if state0 is None:
             ctx.init_state()
         else:
@@ -639,23 +712,28 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
                            overlap=ctx.ordered_stats())
                 if daily_cells is not None:
                     out["daily"] = np.concatenate([ctx.get_daily(k) for k in range(nyears)])
+                if monthly:
+                    out["monthly"] = np.stack([ctx.get_monthly(k) for k in range(nyears)])
                 return out
     if pipelined:
         # a STOP: the reference program ends in that decade, while run_ordered
         # goes on with the other cells; the decade-by-decade form stops there
         return run_cell_order(zi=zi, params=params, forcing=forcing, nisurf=nisurf, year0=year0, nyears=nyears,
                               grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False,
-                              daily_cells=daily_cells)
+                              daily_cells=daily_cells, monthly=monthly)
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device, nslots=10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
         if daily_cells is not None:
             ctx.set_daily(daily_cells)
+        if monthly:
+            ctx.set_monthly(True)
         if state0 is None:
             ctx.init_state()
         else:
             ctx.set_state(state0)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
+        mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
         d0, rc, err, passes, work, daily = 0, 0, None, [], [], []
         for y0, ny in decades(year0, nyears):
             for k in range(ny):
@@ -668,6 +746,9 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             work.append(ctx.decade_stats())
             if daily_cells is not None:
                 daily += [ctx.get_daily(k) for k in range(ny)]
+            if monthly:
+                for k in range(ny):
+                    mon[y0 - year0 + k] = ctx.get_monthly(k)
             rc = ctx.decade_rc
             if rc:
                 err = ctx.last_error()
@@ -676,11 +757,13 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
                    work=work)
         if daily_cells is not None:
             out["daily"] = np.concatenate(daily)
+        if monthly:
+            out["monthly"] = mon
         return out
 
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
-        state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None):
+        state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -690,7 +773,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     after that year, as the reference program would, else the other cells
     go on.  ``errors`` holds every cell's STOP record (Context.get_errors).
     daily_cells: the cells whose daily line is recorded (Context.set_daily)
-    -> out["daily"] (ndays of the years run, 11, nsel)."""
+    -> out["daily"] (ndays of the years run, 11, nsel).  monthly: the month-end
+    snapshots (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n)."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device) as ctx:
@@ -701,7 +785,10 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             ctx.set_state(state0)
         if daily_cells is not None:
             ctx.set_daily(daily_cells)
+        if monthly:
+            ctx.set_monthly(True)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
+        mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
         d0, rc, err, daily = 0, 0, None, []
         for y in range(nyears):
             nt = days_in_year(year0 + y)
@@ -711,6 +798,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             ann[y] = ctx.get_annual()
             if daily_cells is not None:
                 daily.append(ctx.get_daily())
+            if monthly:
+                mon[y] = ctx.get_monthly()
             d0 += nt
             if rc:
                 err = ctx.last_error()
@@ -719,4 +808,6 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
         out = dict(annual=ann, state=ctx.get_state(), rc=rc, err=err, errors=ctx.get_errors())
         if daily_cells is not None:
             out["daily"] = np.concatenate(daily)
+        if monthly:
+            out["monthly"] = mon
         return out

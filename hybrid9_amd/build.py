@@ -16,8 +16,9 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "csrc" / "h9g.hip"
+SRC_MON = HERE / "csrc" / "h9g_mon.hip"     # the monthly kernels: h9g.hip once more, with H9G_MONTHLY_UNIT
 SRC_IO = HERE / "csrc" / "h9g_io.cpp"       # host-only NetCDF I/O
-DEPS = [SRC, SRC_IO, HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
+DEPS = [SRC, SRC_MON, SRC_IO, HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
         HERE / "csrc" / "h9g_synth.h", HERE / "csrc" / "h9g_geo.h",
         HERE / "csrc" / "h9g_pair.h", HERE / "csrc" / "h9g_expr.h", HERE / "csrc" / "h9g_rows.h",
         HERE / "csrc" / "h9g_io.h",
@@ -70,9 +71,10 @@ def _run(cmd, verbose):
 
 
 def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
-    """Compiles the two translation units to objects (the device code, ~4
-    minutes, and the host-only NetCDF I/O, seconds; each only when its own
-    inputs changed, keyed by their digest) and links libh9g.so."""
+    """Compiles the three translation units to objects (the year kernels and
+    the monthly kernels, ~4 minutes each and side by side, and the host-only
+    NetCDF I/O, seconds; each only when its own inputs changed, keyed by
+    their digest) and links libh9g.so."""
     if not force and up_to_date():
         return OUT
     OUT.parent.mkdir(parents=True, exist_ok=True)
@@ -80,9 +82,10 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
     obj.mkdir(exist_ok=True)
     import hashlib
     flags = [f"--offload-arch={ARCH}", *FLAGS, *extra]
-    objs = []
+    objs, jobs = [], []
+    dev = [d for d in DEPS if d not in (SRC_IO, SRC_MON)]
     # h9g_build_id lives in the I/O unit: only it gets the digest flag
-    for src, deps, idf in ((SRC, [d for d in DEPS if d != SRC_IO], []),
+    for src, deps, idf in ((SRC, dev, []), (SRC_MON, [SRC_MON, *dev], []),
                            (SRC_IO, [SRC_IO, HERE / "csrc" / "h9g_io.h", DEPS[-1]], [id_flag(extra)])):
         flags_u = flags + idf
         hs = hashlib.sha256(" ".join(flags_u).encode())
@@ -93,9 +96,13 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
             for old in obj.glob(f"{src.stem}_*.o"):
                 old.unlink()
             tmp = o.with_suffix(".o.tmp")
-            _run([hipcc(), *[f for f in flags_u if f != "-shared"], "-c", str(src), "-o", str(tmp)], verbose)
-            os.replace(tmp, o)
+            jobs.append(([hipcc(), *[f for f in flags_u if f != "-shared"], "-c", str(src), "-o", str(tmp)], tmp, o))
         objs.append(str(o))
+    if jobs:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(len(jobs)) as ex:
+            for _ in ex.map(lambda j: (_run(j[0], verbose), os.replace(j[1], j[2])), jobs):
+                pass
     tmp = OUT.with_suffix(".so.tmp")
     _run([hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", *objs, "-o", str(tmp)], verbose)
     os.replace(tmp, OUT)

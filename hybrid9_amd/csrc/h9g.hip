@@ -138,8 +138,10 @@ constexpr int pair_waves() { return pair_resident<L>(); }
 
 // C: columns (pairs) per wave: 22 (h9g_pair_kernel, h9g_pair2_kernel) or 11
 // (h9g_pair11_kernel: 42 helper lanes, 2 rounds per phase at L = 10).
-template <int L, class G, int R, int C = H9G_PCPW>
-__device__ __forceinline__ void pair_body(const KArgs &a, const G &g) {
+// MON: the monthly kernels (month-end snapshots of the running sums into
+// `mon`, addressed as a.annual: 12 * annual rows per cell).
+template <int L, class G, int R, int C = H9G_PCPW, bool MON = false>
+__device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr) {
   typedef PairStore<L, 2 * C, R> PS;
   __shared__ uint64_t s_e2[32];
   __shared__ double s_l2[32];
@@ -213,6 +215,8 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g) {
     H9K_TS_SUM(L, cs, ts_sum)
     if (!(ts_sum > SOIL_TRUNC) || err[c] != 0) {
       if (h == 0) nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
+      if constexpr (MON)
+        if (h == 0) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
       return;
     }
     cell_inv_pair<L, G>(g, cs);
@@ -228,8 +232,14 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g) {
   if (lane == 0 && a.stamps)
     for (int k = 0; k < 8; k++) a.stamps[(blockIdx.x * H9G_PWAVES + wave) * 8 + k] = pr.acc[k];
 #else
-  const int code = cell_year_pair<L, G>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf,
-                                        a.grow_on, (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw);
+  int code;
+  if constexpr (MON)
+    code = cell_year_pair<L, G, Split2, PS, true, NoProf, Months>(
+        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf, a.grow_on,
+        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, NoProf(), Months{(gbl_float *)(mon + io), ios});
+  else
+    code = cell_year_pair<L, G>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf,
+                                a.grow_on, (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw);
 #endif
   if (spare || h != 0) return;       // the even lane writes the cell back
   int cw = c, iow = io;
@@ -241,6 +251,7 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g) {
   if (code) {
     stop_write(err, n, cw, code, eday, estep, errval, a.err_flag);
     nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);
+    if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);
   }
 }
 
@@ -295,52 +306,109 @@ h9g_pair1_kernel(const KArgs a, const G g) {
 // Solo kernel: one lane per soil column running the generic code of
 // h9g_pair.h with one lane doing every layer (SplitAll: two layers per
 // scheduling region, tridiagonal rows eliminated as assembled).
+// The body is a macro, expanded in place in the kernel and in its monthly
+// sibling (MON, `mon`: pair_body's): as an inlined function the same
+// statements compiled to other machine code for the kernel (blockDim.x loaded
+// from the dispatch packet; as with the row macros of h9g_rows.h).
+#define H9G_SOLO_BODY(MON, mon)                                                                                    \
+  typedef SoloStore<L> SS;                                                                                         \
+  __shared__ uint64_t s_e2[32];                                                                                    \
+  __shared__ double s_l2[32];                                                                                      \
+  __shared__ float s_cell[SS::ROWS * H9G_YBLOCK];                                                                  \
+  __shared__ float s_zt[zt_size<L>()];                                                                             \
+  if (threadIdx.x == 0) fill_zt<L>(g, s_zt);                                                                       \
+  load_tabs(s_e2, s_l2);                                                                                           \
+  const h9m::Tabs T = {s_e2, s_l2};                                                                                \
+  const int slot = a.c0 + (int)(xcd_vwg(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x);                        \
+  if (slot >= a.cend) return;                                                                                      \
+  const int c = a.perm ? a.perm[slot] : slot;                                                                      \
+  const int io = a.sorted_io ? slot : c;                                                                           \
+  const int n = a.ncell;                                                                                           \
+  const size_t ios = a.sorted_io ? a.iostride : (size_t)n;                                                         \
+  SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};                                               \
+  const SplitAll sp;                                                                                               \
+  St<L> s;                                                                                                         \
+  H9K_LOAD_LANE(L, cs, s, a.par, n, c, a.st, n, c)                                                                 \
+  H9K_LOAD_SCALARS(L, s, a.st, n, c)                                                                               \
+  cs.launder();                                                                                                    \
+  H9K_TS_SUM(L, cs, ts_sum)                                                                                        \
+  if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {                                                                   \
+    nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);                                                                  \
+    if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);                                      \
+    return;                                                                                                        \
+  }                                                                                                                \
+  cell_inv_pair<L, G>(g, cs);                                                                                      \
+  int eday = 0, estep = 0;                                                                                         \
+  float errval = 0.0f;                                                                                             \
+  int code;                                                                                                        \
+  if constexpr (MON)                                                                                               \
+    code = cell_year_pair<L, G, SplitAll, SS, false, NoProf, Months>(                                              \
+        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, a.nt, a.nisurf, a.grow_on,                    \
+        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, NoProf(),                                \
+        Months{(gbl_float *)(mon + io), ios});                                                                     \
+  else                                                                                                             \
+    code = cell_year_pair<L, G, SplitAll, SS, false>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar,  \
+                                                     a.nt, a.nisurf, a.grow_on, (gbl_float *)(a.annual + io), ios, \
+                                                     eday, estep, errval, T, a.raw);                               \
+  int cw = c, iow = io;                                                                                            \
+  opaque(cw);                                                                                                      \
+  opaque(iow);                                                                                                     \
+  cs.launder();                                                                                                    \
+  if (a.hist) a.hist[cw] = s.naq;                                                                                  \
+  H9K_STORE_CELL(L, s, cs, a.st, n, cw, a.grow_on, SC_N)                                                           \
+  if (code) {                                                                                                      \
+    stop_write(a.err, n, cw, code, eday, estep, errval, a.err_flag);                                               \
+    nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);                                                                 \
+    if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);                                     \
+  }
+
 template <int L, class G>
 __global__ void __launch_bounds__(H9G_YBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 h9g_solo_kernel(const KArgs a, const G g) {
-  typedef SoloStore<L> SS;
-  __shared__ uint64_t s_e2[32];
-  __shared__ double s_l2[32];
-  __shared__ float s_cell[SS::ROWS * H9G_YBLOCK];
-  __shared__ float s_zt[zt_size<L>()];
-  if (threadIdx.x == 0) fill_zt<L>(g, s_zt);
-  load_tabs(s_e2, s_l2);
-  const h9m::Tabs T = {s_e2, s_l2};
-  const int slot = a.c0 + (int)(xcd_vwg(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x);
-  if (slot >= a.cend) return;
-  const int c = a.perm ? a.perm[slot] : slot;
-  const int io = a.sorted_io ? slot : c;
-  const int n = a.ncell;
-  const size_t ios = a.sorted_io ? a.iostride : (size_t)n;
-  SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};
-  const SplitAll sp;
-  St<L> s;
-  H9K_LOAD_LANE(L, cs, s, a.par, n, c, a.st, n, c)
-  H9K_LOAD_SCALARS(L, s, a.st, n, c)
-  cs.launder();
-  H9K_TS_SUM(L, cs, ts_sum)
-  if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {
-    nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
-    return;
-  }
-  cell_inv_pair<L, G>(g, cs);
-  int eday = 0, estep = 0;
-  float errval = 0.0f;
-  const int code = cell_year_pair<L, G, SplitAll, SS, false>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar,
-                                                             a.nt, a.nisurf, a.grow_on, (gbl_float *)(a.annual + io),
-                                                             ios, eday, estep, errval, T, a.raw);
-  int cw = c, iow = io;
-  opaque(cw);
-  opaque(iow);
-  cs.launder();
-  if (a.hist) a.hist[cw] = s.naq;
-  H9K_STORE_CELL(L, s, cs, a.st, n, cw, a.grow_on, SC_N)
-  if (code) {
-    stop_write(a.err, n, cw, code, eday, estep, errval, a.err_flag);
-    nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);
-  }
+  H9G_SOLO_BODY(false, ((float *)nullptr))
 }
 
+// The monthly kernels (h9g_set_monthly): each year kernel once more under a
+// name of its own, with the Months policy of cell_year_pair and the base of
+// the monthly rows as an argument after KArgs -- KArgs itself is unchanged, so
+// the kernels above keep their argument layout and their machine code.
+// Launched only by a context with monthly recording on, never by a probe.
+template <int L, class G>
+__global__ void __launch_bounds__(64 * H9G_PWAVES)
+    __attribute__((amdgpu_waves_per_eu(pair_waves<L>(), pair_waves<L>())))
+h9g_pair_mon_kernel(const KArgs a, float *mon, const G g) {
+  pair_body<L, G, pair_waves<L>(), H9G_PCPW, true>(a, g, mon);
+}
+template <int L, class G>
+__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
+h9g_pair2_mon_kernel(const KArgs a, float *mon, const G g) {
+  pair_body<L, G, 2, H9G_PCPW, true>(a, g, mon);
+}
+template <int L, class G>
+__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(3, 3)))
+h9g_pair11_mon_kernel(const KArgs a, float *mon, const G g) {
+  pair_body<L, G, 3, H9G_PCPW11, true>(a, g, mon);
+}
+template <int L, class G>
+__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(1, 1)))
+h9g_pair1_mon_kernel(const KArgs a, float *mon, const G g) {
+  pair_body<L, G, 1, 1, true>(a, g, mon);
+}
+template <int L, class G>
+__global__ void __launch_bounds__(H9G_YBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
+h9g_solo_mon_kernel(const KArgs a, float *mon, const G g) {
+  H9G_SOLO_BODY(true, mon)
+}
+
+// The monthly kernels are compiled in a translation unit of their own
+// (h9g_mon.hip: this file with H9G_MONTHLY_UNIT, which keeps the year
+// kernels' code above, the kernel kinds and the geometry dispatch below, and
+// h9g_mon_launch), beside this one, so the two build at the same time.
+int h9g_mon_launch(int kind, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream, const KArgs &a,
+                   float *mon);
+int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);
+
+#if !defined(H9G_MONTHLY_UNIT)
 // The year's forcing in the year kernel's slot order (round 4, VERDICT r03
 // #5): dst[v][d][s] = src[v][d][perm[s]].  With the cells re-ordered each
 // year (h9g_sort_kernel), a wave's daily forcing loads by cell id scattered
@@ -1008,6 +1076,8 @@ __global__ void h9g_math_fast_kernel(int n, const float *x, const float *y, floa
   flag[i] = mf.redone ? 1 : 0;
 }
 
+#endif  // !H9G_MONTHLY_UNIT
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -1114,6 +1184,15 @@ struct h9g_ctx {
   size_t fyrs_cap = 0;
   std::vector<FocusYear> h_fyrs;
   std::vector<int> daily_nt;      // days of each year recorded by the last call
+  // monthly output (h9g_set_monthly / h9g_get_monthly; the monthly kernels)
+  int monthly = 0;                // recording on
+  float *d_mon = nullptr;         // a year's month-end snapshots, 12 x annual rows of n (as d_ann)
+  float *d_mon_s = nullptr;       // ... in slot order (as d_ann_s)
+  float *d_mon_ret = nullptr;     // an ordered call's years, (years, 12, annual rows, n)
+  size_t mon_ret_cap = 0;         // years allocated there
+  int mon_base = 0;               // first year of the running ordered call there
+  int mon_years = 0;              // years recorded by the last call (0: none)
+  bool mon_in_ret = false;        // ... in d_mon_ret (an ordered call) or d_mon (h9g_run_year)
 };
 
 static void ord_free(h9g_ctx *ctx);
@@ -1216,6 +1295,39 @@ template __global__ void h9g_pair11_kernel<10, GeoC<10, 24>>(const KArgs, const 
 template __global__ void h9g_pair1_kernel<8, GeoC<8, 48>>(const KArgs, const GeoC<8, 48>);
 template __global__ void h9g_pair_kernel<8, GeoC<8, 48>>(const KArgs, const GeoC<8, 48>);
 #endif
+#elif defined(H9G_MONTHLY_UNIT)
+// The cell order: the cells that start a decade stopped (err0) run none
+// of its years; all their monthly rows of the decade (`rows` of n) are NaN.
+__global__ void __launch_bounds__(256) h9g_stopped_mon_kernel(int n, int rows, const int *__restrict__ err0,
+                                                              float *__restrict__ mon) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n || err0[c] == 0) return;
+  for (int r = 0; r < rows; r++) mon[(size_t)r * n + c] = __builtin_nanf("");
+}
+
+int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream) {
+  h9g_stopped_mon_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(n, rows, err0, mon);
+  return 0;
+}
+
+// The monthly kernel of a launch of `kind` (not K_MIXED: launch_year cuts
+// that into its two parts) with the configuration's geometry variant.
+int h9g_mon_launch(int kind, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream, const KArgs &a,
+                   float *mon) {
+  const struct { int L; h9g_config cfg; } c{cfg->nlayers, *cfg};
+  switch (kind) {
+    case K_SOLO: H9G_DISPATCH(&c, h9g_solo_mon_kernel, grid, block, stream, a, mon); break;
+    case K_PAIR2:
+      if (c.L != 10) return H9G_EINVAL;
+      H9G_DISPATCH_L10(&c, h9g_pair2_mon_kernel, grid, block, stream, a, mon);
+      break;
+    case K_PAIR11: H9G_DISPATCH(&c, h9g_pair11_mon_kernel, grid, block, stream, a, mon); break;
+    case K_PAIR1: H9G_DISPATCH(&c, h9g_pair1_mon_kernel, grid, block, stream, a, mon); break;
+    case K_PAIR: H9G_DISPATCH(&c, h9g_pair_mon_kernel, grid, block, stream, a, mon); break;
+    default: return H9G_EINVAL;
+  }
+  return 0;
+}
 #else
 static unsigned nblocks(size_t n) { return (unsigned)((n + H9G_BLOCK - 1) / H9G_BLOCK); }
 
@@ -1254,6 +1366,9 @@ void h9g_destroy(h9g_ctx *ctx) {
   (void)hipFree(ctx->d_perm2);
   (void)hipFree(ctx->d_forc_s);
   (void)hipFree(ctx->d_ann_s);
+  (void)hipFree(ctx->d_mon);
+  (void)hipFree(ctx->d_mon_s);
+  (void)hipFree(ctx->d_mon_ret);
   (void)hipFree(ctx->d_hist);
   (void)hipFree(ctx->d_aqbits);
   (void)hipFree(ctx->d_pace);
@@ -1670,6 +1785,7 @@ struct YearSpec {
   const int *d_list = nullptr;   // null: every cell, in h9g_sort_kernel's order; else the m cells d_list[0..m)
   int m = 0;
   float *ann_dst = nullptr;      // list launches: their annual means into these rows (stride n, cell order)
+  float *mon_dst = nullptr;      // ... and, with monthly recording on, their month-end snapshots into these
   float *st = nullptr;           // the cells' state and STOP rows (null: the context's own)
   int *err = nullptr;
   bool bulk = false;             // a list launch that is a year of the context's cells (h9g_run_ordered's
@@ -1681,7 +1797,7 @@ struct YearSpec {
   // decade's years)
   const int *h2 = nullptr;
   int k2 = 0, slot2 = 0, jyear2 = 0;
-  float *st2 = nullptr, *ann2 = nullptr;
+  float *st2 = nullptr, *ann2 = nullptr, *mon2 = nullptr;   // (mon2: with monthly recording on)
   int *err2 = nullptr;
   // list launches: only the year's first `ndays` days (0: all), the annual
   // rows as undivided running sums (the cell order's day-1 probe)
@@ -1724,8 +1840,17 @@ static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
 
 // The year kernel of a launch of `kind` over a's slots: `blocks` workgroups
 // of its pair part; the mixed kind over year_ranges' two.
-static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks) {
+// mon: the base of the launch's monthly rows; then the kind's monthly kernel.
+static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks, float *mon) {
   const unsigned pb = (unsigned)blocks, pt = 64 * H9G_PWAVES;
+  if (mon && kind != K_MIXED) {
+    const bool solo = kind == K_SOLO;
+    if (int rc = h9g_mon_launch(kind, &ctx->cfg, solo ? (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK) : pb,
+                                solo ? H9G_YBLOCK : pt, ctx->sc, a, mon))
+      return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   switch (kind) {
     case K_SOLO:   // (no second group on the solo kernel: [c0, cend) is the launch)
       H9G_DISPATCH(ctx, h9g_solo_kernel, (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK), H9G_YBLOCK,
@@ -1737,7 +1862,7 @@ static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks) {
       for (int i = 0; i < nr; i++) {
         a.c0 = r[i].c0;
         a.cend = a.bend = a.split = r[i].cend;
-        if (int rc = launch_year(ctx, r[i].kind, a, blocks)) return rc;
+        if (int rc = launch_year(ctx, r[i].kind, a, blocks, mon)) return rc;
       }
       return 0;
     }
@@ -1763,6 +1888,8 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
               !g2_fits(ctx, d_list ? (size_t)m : ctx->n, (size_t)ys.k2)))
     return H9G_EINVAL;
   if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
+  const bool mon = ctx->monthly && !ys.probe;   // (a probe never records months)
+  if (mon && ((d_list && !ys.mon_dst) || (two && !ys.mon2))) return H9G_EINVAL;
 #if defined(H9G_DUMP_AQ)
   if (d_list || ys.st) return H9G_EINVAL;   // (the record is indexed by the annual array's cell)
 #endif
@@ -1777,6 +1904,11 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (two) HIPCHK(hipStreamWaitEvent(ctx->sc, ctx->ev_copied[ys.slot2], 0));
   const int n = (int)ctx->n;
   const size_t ios = ctx->ios;
+  const size_t mrows = (size_t)H9G_NMONTHS * annual_rows(ctx->L);
+  if (mon && !ctx->d_mon) {                 // NaN until a year writes it, as d_ann
+    HIPCHK(hipMalloc(&ctx->d_mon, sizeof(float) * mrows * ctx->n));
+    HIPCHK(hipMemsetAsync(ctx->d_mon, 0xff, sizeof(float) * mrows * ctx->n, ctx->sc));
+  }
   KArgs a;
   a.ncell = n;
   a.c0 = 0;
@@ -1810,6 +1942,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (d_list || ctx->sort) {
     if (!ctx->d_forc_s) HIPCHK(hipMalloc(&ctx->d_forc_s, sizeof(float) * 7 * (size_t)ctx->cfg.max_days * ios));
     if (!ctx->d_ann_s) HIPCHK(hipMalloc(&ctx->d_ann_s, sizeof(float) * annual_rows(ctx->L) * ios));
+    if (mon && !ctx->d_mon_s) HIPCHK(hipMalloc(&ctx->d_mon_s, sizeof(float) * mrows * ios));
   }
   const size_t dvar = (size_t)ctx->cfg.max_days * ios;
   // the second group from the first whole wave after the first group's
@@ -1872,6 +2005,8 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
 #endif
   }
   if (a.sorted_io) a.fvar = dvar;
+  // the monthly rows, addressed as a.annual
+  float *const mon_a = !mon ? nullptr : a.sorted_io ? ctx->d_mon_s : ctx->d_mon;
   // workgroups of the launch (the pair part's, for the mixed kind)
   const size_t per_block = (size_t)ki.block_cells;
   const size_t blocks = kind == K_MIXED ? (ctx->n - ctx->n_solo + per_block - 1) / per_block
@@ -1938,7 +2073,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   ctx->ev_kind[e] = ys.probe ? K_PROBE : kind;
   ctx->ev_cells[e] = (int64_t)ncells + (two ? ys.k2 : 0);
   HIPCHK(hipEventRecord(ctx->ev0[e], ctx->sc));
-  if (int r = launch_year(ctx, kind, a, blocks)) return r;
+  if (int r = launch_year(ctx, kind, a, blocks, mon_a)) return r;
   HIPCHK(hipEventRecord(ctx->ev1[e], ctx->sc));
   HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot], ctx->sc));
   if (two) HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot2], ctx->sc));
@@ -1949,6 +2084,13 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     if (two)
       h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
           ys.k2, n, (int)rows, a.split, ios, a.perm, ctx->d_ann_s, ys.ann2);
+    if (mon) {
+      h9g_unperm_annual_kernel<<<dim3((unsigned)((ncells + 255) / 256), rows), 256, 0, ctx->sc>>>(
+          (int)ncells, n, (int)mrows, 0, ios, a.perm, ctx->d_mon_s, d_list ? ys.mon_dst : ctx->d_mon);
+      if (two)
+        h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
+            ys.k2, n, (int)mrows, a.split, ios, a.perm, ctx->d_mon_s, ys.mon2);
+    }
     HIPCHK(hipGetLastError());
   }
   if (!d_list || ys.bulk) {
@@ -2104,7 +2246,55 @@ int h9g_run_year(h9g_ctx *ctx, int slot, int jyear) {
   YearSpec ys;
   ys.slot = slot;
   ys.jyear = jyear;
-  return run_year_impl(ctx, ys);
+  if (ctx) ctx->mon_years = 0;
+  const int r = run_year_impl(ctx, ys);
+  if (r == 0 && ctx->monthly) {
+    ctx->mon_years = 1;
+    ctx->mon_in_ret = false;
+  }
+  return r;
+}
+
+int h9g_set_monthly(h9g_ctx *ctx, int on) {
+  if (!ctx) return H9G_EINVAL;
+#if defined(H9G_STAMPS)
+  if (on) return H9G_EINVAL;   // (the phase-stamp measurement build profiles the year kernels proper)
+#endif
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  ctx->monthly = on ? 1 : 0;
+  ctx->mon_years = 0;
+  return 0;
+}
+
+int h9g_get_monthly(h9g_ctx *ctx, int k, float *out) {
+  if (!ctx || !out) return H9G_EINVAL;
+  if (ctx->mon_years < 1) return H9G_ESTATE;
+  if (k < 0 || k >= ctx->mon_years) return H9G_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  const size_t year = (size_t)H9G_NMONTHS * annual_rows(ctx->L) * ctx->n;
+  HIPCHK(hipMemcpy(out, ctx->mon_in_ret ? ctx->d_mon_ret + (size_t)k * year : ctx->d_mon, sizeof(float) * year,
+                   hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Room for the snapshots of an ordered call's `nyears` years; none recorded yet.
+static int mon_begin(h9g_ctx *ctx, int nyears) {
+  ctx->mon_years = 0;
+  ctx->mon_base = 0;
+  if (ctx->mon_ret_cap >= (size_t)nyears) return 0;
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  (void)hipFree(ctx->d_mon_ret);
+  ctx->d_mon_ret = nullptr;
+  ctx->mon_ret_cap = 0;
+  if (hipMalloc(&ctx->d_mon_ret, sizeof(float) * (size_t)nyears * H9G_NMONTHS * annual_rows(ctx->L) * ctx->n) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return H9G_ENOMEM;
+  }
+  ctx->mon_ret_cap = (size_t)nyears;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -2146,6 +2336,8 @@ int h9g_run_year(h9g_ctx *ctx, int slot, int jyear) {
 struct OrdDec {
   int y0 = 0, ny = 0, k0 = 0;            // first year, years, index of its first year in the call
   float *st0 = nullptr, *guess = nullptr, *ann = nullptr, *ck = nullptr;
+  float *mon = nullptr;                  // monthly recording: the snapshots beside ann, (years, 12, annual rows, n)
+  int mon_cap = 0;                       // years allocated there
   int *err0 = nullptr, *eck = nullptr, *dirty = nullptr;
   int *d_chain = nullptr, *d_pred = nullptr, *d_first = nullptr, *d_list = nullptr, *d_flag = nullptr;
   std::vector<int> chain, list, flag;
@@ -2170,7 +2362,7 @@ static void ord_free(h9g_ctx *ctx) {
   OrdBufs *o = ctx->ord;
   if (!o) return;
   for (OrdDec &D : o->d) {
-    for (float *p : {D.st0, D.guess, D.ann, D.ck}) (void)hipFree(p);
+    for (float *p : {D.st0, D.guess, D.ann, D.ck, D.mon}) (void)hipFree(p);
     for (int *p : {D.err0, D.eck, D.dirty, D.d_chain, D.d_pred, D.d_first, D.d_list, D.d_flag}) (void)hipFree(p);
   }
   (void)hipFree(o->st2);
@@ -2229,6 +2421,25 @@ static float *ord_ck(const h9g_ctx *ctx, const OrdDec &D, int y) {
 }
 static int *ord_eck(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.eck + (size_t)y * STOP_ROWS * ctx->n; }
 static float *ord_ann(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.ann + (size_t)y * annual_rows(ctx->L) * ctx->n; }
+// The monthly rows of a decade's year: they live beside its annual rows, and
+// every launch that writes the one writes the other (null with recording off).
+static float *ord_mon(const h9g_ctx *ctx, const OrdDec &D, int y) {
+  return ctx->monthly ? D.mon + (size_t)y * H9G_NMONTHS * annual_rows(ctx->L) * ctx->n : nullptr;
+}
+static int ord_mon_alloc(h9g_ctx *ctx, int ny) {
+  for (OrdDec &D : ctx->ord->d) {
+    if (D.mon && D.mon_cap >= ny) continue;
+    (void)hipFree(D.mon);
+    D.mon = nullptr;
+    D.mon_cap = 0;
+    if (hipMalloc(&D.mon, sizeof(float) * (size_t)ny * H9G_NMONTHS * annual_rows(ctx->L) * ctx->n) != hipSuccess) {
+      (void)hipGetLastError();
+      return H9G_ENOMEM;
+    }
+    D.mon_cap = ny;
+  }
+  return 0;
+}
 
 // The decade's chains (h9g_set_chains) over its land cells that have not
 // stopped when it starts (its final err0), in context order: predecessors
@@ -2400,6 +2611,7 @@ static int ord_run_alone(h9g_ctx *ctx, OrdDec &D, const int32_t *slots, OrdStats
   ys.d_list = D.d_list;
   ys.m = (int)D.list.size();
   ys.ann_dst = ord_ann(ctx, D, D.next_y);
+  ys.mon_dst = ord_mon(ctx, D, D.next_y);
   ys.st = ctx->ord->st2;
   ys.err = ctx->ord->err2;
   if (int r = run_year_impl(ctx, ys)) return r;
@@ -2450,10 +2662,16 @@ static int ord_finish(h9g_ctx *ctx, OrdDec &D, OrdDec *N, float *annual, int &st
       break;
     }
   }
+  if (ctx->monthly)       // the settled decade's months into the call's retained buffer
+    HIPCHK(hipMemcpyAsync(ctx->d_mon_ret + (size_t)(ctx->mon_base + D.k0) * H9G_NMONTHS * rows * n, D.mon,
+                          sizeof(float) * (size_t)D.ny * H9G_NMONTHS * rows * n, hipMemcpyDeviceToDevice, ctx->sc));
   if (N) {
     h9g_settle_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->sc>>>(
         (int)n, srows, rows, N->ny, ord_ck(ctx, D, D.ny - 1), ord_eck(ctx, D, D.ny - 1), N->st0, N->err0, N->dirty,
         ctx->d_st, ctx->d_err, ord_ck(ctx, *N, N->ny - 1), ord_eck(ctx, *N, N->ny - 1), N->ann);
+    // NaN months where it wrote NaN means: a cell that starts N stopped runs
+    // none of N's years (N's first pass is done, and its chains leave it out)
+    if (ctx->monthly) h9g_mon_stopped((int)n, N->ny * H9G_NMONTHS * rows, N->err0, N->mon, ctx->sc);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(ctx->sc));
@@ -2499,6 +2717,8 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   if (int r = ord_alloc(ctx, nymax)) return r;
+  if (ctx->monthly)
+    if (int r = ord_mon_alloc(ctx, nymax)) return r;
   OrdBufs *o = ctx->ord;
   // land cells (HYBRID9.f90:122-123, summed in layer order as the year
   // kernels do)
@@ -2567,6 +2787,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
         ys.m = nb;
         ys.bulk = true;
         ys.ann_dst = ctx->d_ann;
+        ys.mon_dst = ctx->d_mon;
       }
       const bool ride = P && P->phase == OrdDec::RERUN && g2_fits(ctx, (size_t)nb, P->list.size()) &&
                         !getenv("H9G_NO_RIDE");
@@ -2578,10 +2799,14 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
         ys.st2 = o->st2;
         ys.err2 = o->err2;
         ys.ann2 = ord_ann(ctx, *P, P->next_y);
+        ys.mon2 = ord_mon(ctx, *P, P->next_y);
       }
       if (int r = run_year_impl(ctx, ys)) return r;
       S.ticks++;
       HIPCHK(hipMemcpyAsync(ord_ann(ctx, D, y), ctx->d_ann, sizeof(float) * rows * n, hipMemcpyDeviceToDevice, ctx->sc));
+      if (ctx->monthly)
+        HIPCHK(hipMemcpyAsync(ord_mon(ctx, D, y), ctx->d_mon, sizeof(float) * H9G_NMONTHS * rows * n,
+                              hipMemcpyDeviceToDevice, ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_ck(ctx, D, y), ctx->d_st, sizeof(float) * srows * n, hipMemcpyDeviceToDevice, ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_eck(ctx, D, y), ctx->d_err, sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToDevice, ctx->sc));
       if (ride) {
@@ -2646,6 +2871,10 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
                          S.alone_cell_years, S.excluded, S.probed, S.probe_kept};
   std::copy(os, os + 9, ctx->ord_stats);
   ctx->ord_passes = S.dec_passes;
+  if (ctx->monthly) {
+    ctx->mon_years = ctx->mon_base + nyears;
+    ctx->mon_in_ret = true;
+  }
   // the first STOP of the call (h9g_last_error) or one from before it
   return h9g_sync(ctx);
 }
@@ -2670,11 +2899,15 @@ int h9g_run_decade_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int n
     HIPCHK(hipSetDevice(ctx->device));
     if (int r = daily_begin(ctx, jyear0, nyears)) return r;
   }
+  if (ctx && ctx->monthly)
+    if (int r = mon_begin(ctx, nyears)) return r;
   return run_ordered_impl(ctx, slots, jyear0, {{jyear0, nyears}}, annual, passes);
 }
 
 int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, float *annual, int32_t *passes) {
   if (nyears < 1 || jyear0 < 1861) return H9G_EINVAL;
+  if (ctx && ctx->monthly)
+    if (int r = mon_begin(ctx, nyears)) return r;
   if (ctx && !ctx->daily_sel.empty()) {
     // with a selection the decades run one after another, each as
     // h9g_run_decade_ordered runs it (the same results bit for bit), and each
@@ -2688,6 +2921,7 @@ int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, 
     const size_t rows = annual_rows(ctx->L);
     int first = 0, k0 = 0, i = 0;
     for (const auto &d : ref_decades(jyear0, nyears)) {
+      ctx->mon_base = k0;
       const int r = run_ordered_impl(ctx, slots + k0, d.first, {d}, annual ? annual + (size_t)k0 * rows * ctx->n : nullptr,
                                      passes ? passes + i : nullptr);
       if (r < 0) return r;

@@ -720,6 +720,73 @@ int write_cdf2(const char *path, const std::vector<std::pair<std::string, uint32
   return ok ? 0 : H9G_EINVAL;
 }
 
+// The fields of WRITE_NET_CDF_3DR.f90 for the cells `gid` (grid ids iy*nx+ix,
+// latitude row iy from the north, INIT.f90:142-145) as a CDF-2 file; every
+// other grid cell is the NaN fill.  vals: (12+L) rows of ncell
+// (h9g_get_annual's order) -- one set (nm = 0: axyYYYY.nc, the reference's
+// file) or nm sets under a leading dimension `month` (mxyYYYY.nc).
+int write_xy_nc(const char *path, int nx, int ny, int L, const float *zc, int ncell, const int64_t *gid,
+                const float *vals, int nm, const char *npp_units) {
+  const float nan = std::nanf("");
+  const int M = nm > 0 ? 1 : 0, sets = nm > 0 ? nm : 1, rows = 12 + L;
+  // dims in definition order (WRITE_NET_CDF_3DR.f90:101-103)
+  std::vector<std::pair<std::string, uint32_t>> dims;
+  if (M) dims.push_back({"month", (uint32_t)nm});
+  dims.push_back({"latitude", (uint32_t)ny});
+  dims.push_back({"longitude", (uint32_t)nx});
+  dims.push_back({"layer_centre_depth", (uint32_t)L});
+  const int D_LAT = M, D_LON = M + 1, D_Z = M + 2;
+  // (name, units, row) of the 2-D fields (:53-77, :142-180)
+  struct F2 { const char *name, *units; int row; };
+  const F2 f2[] = {{"net primary production", npp_units, 0},
+                   {"plant mass", "g[DM]", 1},
+                   {"runoff", "mm/s", 2},
+                   {"evaporation", "mm/s", 3},
+                   {"temperature", "K", 4},
+                   {"specific_humidity", "kg[water]/kg[air]", 7},
+                   {"air_pressure", "Pa", 8},
+                   {"precipitation", "kg/m^2/s", 9},
+                   {"relative_humidity", "percent", 10},
+                   {"soil_water", "mm", 11 + L}};
+  auto with_month = [&](std::vector<int> d) {
+    if (M) d.insert(d.begin(), 0);
+    return d;
+  };
+  const uint64_t plane = (uint64_t)nx * ny;
+  std::vector<WVar> vars;
+  vars.push_back({"latitude", {D_LAT}, {text_att("units", "degrees_north")}, (uint64_t)ny});
+  vars.push_back({"longitude", {D_LON}, {text_att("units", "degrees_east")}, (uint64_t)nx});
+  vars.push_back({"layer_centre_depth", {D_Z}, {text_att("units", "mm")}, (uint64_t)L});
+  for (const F2 &v : f2)
+    vars.push_back({v.name, with_month({D_LAT, D_LON}), {text_att("units", v.units), float_att("_FillValue", nan)},
+                    plane * sets});
+  vars.push_back({"soil_water_layers", with_month({D_LAT, D_LON, D_Z}),
+                  {text_att("units", "mm^3/mm^3"), float_att("_FillValue", nan)}, plane * L * sets});
+  const float dlon = 360.0f / (float)nx, dlat = 180.0f / (float)ny;
+  return write_cdf2(path, dims, vars, [&](size_t k, float *out) {
+    const uint64_t n = vars[k].nel;
+    if (k == 0) {                                // INIT.f90:145 lat_all(y) = 89.75 - (y-1)*0.5
+      for (int y = 0; y < ny; y++) out[y] = (90.0f - 0.5f * dlat) - (float)y * dlat;
+    } else if (k == 1) {                         // INIT.f90:142 lon_all(x) = -179.75 + (x-1)*0.5
+      for (int x = 0; x < nx; x++) out[x] = (-180.0f + 0.5f * dlon) + (float)x * dlon;
+    } else if (k == 2) {                         // zc_o (INIT.f90:262)
+      for (int i = 0; i < L; i++) out[i] = zc ? zc[i] : nan;
+    } else if (k < 3 + sizeof(f2) / sizeof(f2[0])) {
+      for (uint64_t i = 0; i < n; i++) out[i] = nan;
+      const int row = f2[k - 3].row;
+      for (int m = 0; m < sets; m++)
+        for (int c = 0; c < ncell; c++)
+          out[(uint64_t)m * plane + gid[c]] = vals[((size_t)m * rows + row) * ncell + c];
+    } else {                                     // soil_water_layers ([month,] lat, lon, z)
+      for (uint64_t i = 0; i < n; i++) out[i] = nan;
+      for (int m = 0; m < sets; m++)
+        for (int c = 0; c < ncell; c++)
+          for (int i = 0; i < L; i++)
+            out[((uint64_t)m * plane + gid[c]) * L + i] = vals[((size_t)m * rows + 11 + i) * ncell + c];
+    }
+  });
+}
+
 }  // namespace
 
 // --------------------------------------------------------------- C-ABI
@@ -741,54 +808,35 @@ int h9g_write_axy_nc(const char *path, int nx, int ny, int nlayers, const float 
                      const int64_t *gid, const float *annual) {
   if (!path || nx <= 0 || ny <= 0 || nlayers < 1 || nlayers > H9G_LMAX || ncell < 0 || (ncell && (!gid || !annual)))
     return H9G_EINVAL;
-  const int L = nlayers;
   for (int c = 0; c < ncell; c++)
     if (gid[c] < 0 || gid[c] >= (int64_t)nx * ny) return H9G_EINVAL;
-  const float nan = std::nanf("");
-  // dims in definition order (WRITE_NET_CDF_3DR.f90:101-103)
-  const std::vector<std::pair<std::string, uint32_t>> dims = {
-      {"latitude", (uint32_t)ny}, {"longitude", (uint32_t)nx}, {"layer_centre_depth", (uint32_t)L}};
-  enum { D_LAT = 0, D_LON = 1, D_Z = 2 };
-  // (name, units, annual row) of the 2-D fields (:53-77, :142-180)
-  struct F2 { const char *name, *units; int row; };
-  const F2 f2[] = {{"net primary production", "g[DM]/m^2/yr", 0},
-                   {"plant mass", "g[DM]", 1},
-                   {"runoff", "mm/s", 2},
-                   {"evaporation", "mm/s", 3},
-                   {"temperature", "K", 4},
-                   {"specific_humidity", "kg[water]/kg[air]", 7},
-                   {"air_pressure", "Pa", 8},
-                   {"precipitation", "kg/m^2/s", 9},
-                   {"relative_humidity", "percent", 10},
-                   {"soil_water", "mm", 11 + L}};
-  std::vector<WVar> vars;
-  vars.push_back({"latitude", {D_LAT}, {text_att("units", "degrees_north")}, (uint64_t)ny});
-  vars.push_back({"longitude", {D_LON}, {text_att("units", "degrees_east")}, (uint64_t)nx});
-  vars.push_back({"layer_centre_depth", {D_Z}, {text_att("units", "mm")}, (uint64_t)L});
-  for (const F2 &v : f2)
-    vars.push_back({v.name, {D_LAT, D_LON}, {text_att("units", v.units), float_att("_FillValue", nan)},
-                    (uint64_t)nx * ny});
-  vars.push_back({"soil_water_layers", {D_LAT, D_LON, D_Z},
-                  {text_att("units", "mm^3/mm^3"), float_att("_FillValue", nan)}, (uint64_t)nx * ny * L});
-  const float dlon = 360.0f / (float)nx, dlat = 180.0f / (float)ny;
-  return write_cdf2(path, dims, vars, [&](size_t k, float *out) {
-    const uint64_t n = vars[k].nel;
-    if (k == 0) {                                // INIT.f90:145 lat_all(y) = 89.75 - (y-1)*0.5
-      for (int y = 0; y < ny; y++) out[y] = (90.0f - 0.5f * dlat) - (float)y * dlat;
-    } else if (k == 1) {                         // INIT.f90:142 lon_all(x) = -179.75 + (x-1)*0.5
-      for (int x = 0; x < nx; x++) out[x] = (-180.0f + 0.5f * dlon) + (float)x * dlon;
-    } else if (k == 2) {                         // zc_o (INIT.f90:262)
-      for (int i = 0; i < L; i++) out[i] = zc ? zc[i] : nan;
-    } else if (k < 3 + sizeof(f2) / sizeof(f2[0])) {
-      for (uint64_t i = 0; i < n; i++) out[i] = nan;
-      const int row = f2[k - 3].row;
-      for (int c = 0; c < ncell; c++) out[gid[c]] = annual[(size_t)row * ncell + c];
-    } else {                                     // soil_water_layers (lat, lon, z)
-      for (uint64_t i = 0; i < n; i++) out[i] = nan;
-      for (int c = 0; c < ncell; c++)
-        for (int i = 0; i < L; i++) out[(size_t)gid[c] * L + i] = annual[(size_t)(11 + i) * ncell + c];
+  return write_xy_nc(path, nx, ny, nlayers, zc, ncell, gid, annual, 0, "g[DM]/m^2/yr");
+}
+
+// mxyYYYY.nc: the monthly means of year jyear from its month-end snapshots
+// (h9g_get_monthly: the year's running sums, undivided), axyYYYY.nc's fields
+// under a leading dimension month.  mean = (S[m] - S[m-1]) / days_m in double
+// (S[-1] = 0), rounded to float; the divisor is days_m * nisurf for runoff and
+// 1 for net primary production (a monthly total).
+int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers, const float *zc, int ncell,
+                     const int64_t *gid, int jyear, int nisurf, const float *snapshots) {
+  if (!path || nx <= 0 || ny <= 0 || nlayers < 1 || nlayers > H9G_LMAX || ncell < 0 || nisurf < 1 ||
+      (ncell && (!gid || !snapshots)))
+    return H9G_EINVAL;
+  for (int c = 0; c < ncell; c++)
+    if (gid[c] < 0 || gid[c] >= (int64_t)nx * ny) return H9G_EINVAL;
+  const int rows = 12 + nlayers;
+  const bool leap = jyear % 4 == 0 && (jyear % 100 != 0 || jyear % 400 == 0);   // INIT.f90:844-859
+  const int mdays[H9G_NMONTHS] = {31, leap ? 29 : 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
+  std::vector<float> mean((size_t)H9G_NMONTHS * rows * ncell);
+  for (int m = 0; m < H9G_NMONTHS; m++)
+    for (int k = 0; k < rows; k++) {
+      const double div = k == 0 ? 1.0 : k == 2 ? (double)mdays[m] * (double)nisurf : (double)mdays[m];
+      const float *s1 = snapshots + ((size_t)m * rows + k) * ncell, *s0 = m ? s1 - (size_t)rows * ncell : nullptr;
+      float *o = mean.data() + ((size_t)m * rows + k) * ncell;
+      for (int c = 0; c < ncell; c++) o[c] = (float)(((double)s1[c] - (s0 ? (double)s0[c] : 0.0)) / div);
     }
-  });
+  return write_xy_nc(path, nx, ny, nlayers, zc, ncell, gid, mean.data(), H9G_NMONTHS, "g[DM]/m^2/month");
 }
 
 // READ_PGF.f90 + READ_NET_CDF_3DR.f90 for the cells of a context: days

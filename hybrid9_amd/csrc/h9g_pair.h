@@ -2230,14 +2230,65 @@ H9K_HD int substep_pair(const G &g, CS cs, const SP &sp, St<L> &s, float &rnf_su
   return code;
 }
 
+// Monthly output: what cell_year_pair does at the end of a
+// day besides the reference's sums.  The month (0..11) that ends with day d1
+// (1-based) of a year of nt days in the calendar of INIT.f90:844-859, or -1.
+// From nt alone: the two groups of a launch run different calendar years.
+H9K_HD int month_end(int d1, int nt) {
+  if (d1 == 31) return 0;
+  switch (d1 - (nt == 366 ? 1 : 0)) {      // from February on
+    case 59: return 1;
+    case 90: return 2;
+    case 120: return 3;
+    case 151: return 4;
+    case 181: return 5;
+    case 212: return 6;
+    case 243: return 7;
+    case 273: return 8;
+    case 304: return 9;
+    case 334: return 10;
+    case 365: return 11;
+    default: return -1;
+  }
+}
+// NoMonths: nothing (every kernel but the monthly ones).
+struct NoMonths {
+  template <int L>
+  H9K_HD void day_end(int, int, const gbl_float *, size_t, float) const {}
+};
+// Months: at a month's last day, the year's 12 + L running sums as they
+// stand -- after GROW and the day's additions, undivided (the form `raw`
+// gives the day-1 probe) -- into the cell's monthly rows: value k of month
+// m at M[(m * (12 + L) + k) * stride].  rnf_sum comes from its register; row
+// evap is the reference's zero (it never accumulates evap_sum); the others
+// are read back from the annual rows A, which the day has just stored.  The
+// sums are not reset: the year's sums stay the reference's, and a month's
+// mean is the difference of two snapshots (h9g.h).  Called by active lanes
+// only, once a day, outside the substep loop; the test is wave-uniform.
+struct Months {
+  gbl_float *M;
+  size_t stride;
+  template <int L>
+  H9K_HD void day_end(int day, int nt, const gbl_float *A, size_t as, float rnf_sum) const {
+    const int m = month_end(day + 1, nt);
+    if (m < 0) return;
+    gbl_float *o = M + (size_t)m * (12 + L) * stride;
+    float v[12 + L];
+#pragma unroll
+    for (int k = 0; k < 12 + L; k++) v[k] = k == 2 ? rnf_sum : k == 3 ? zero : A[k * as];
+#pragma unroll
+    for (int k = 0; k < 12 + L; k++) o[k * stride] = v[k];
+  }
+};
+
 // One calendar year for one cell (HYBRID9.f90:150-290), as cell_year.
 // Park = keep the plant state in the store over the substeps (register
-// relief for the 168-VGPR pair kernel).
-template <int L, class G, class SP, class CS, bool Park = true, class PR = NoProf>
+// relief for the 168-VGPR pair kernel).  MO: NoMonths or Months.
+template <int L, class G, class SP, class CS, bool Park = true, class PR = NoProf, class MO = NoMonths>
 H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_float *forc, size_t fday,
                           size_t fvar, int nt, int nisurf, int grow_on, gbl_float *acc, size_t astride,
                           int &eday, int &estep, float &errval, const h9m::Tabs &T, int raw = 0,
-                          PR &&pr = PR()) {
+                          PR &&pr = PR(), MO mo = MO()) {
   enum { A_NPP = 0, A_PM, A_RNF, A_EVAP, A_TAS, A_RLDS, A_RSDS, A_HUSS, A_PS, A_PR, A_RHS,
          A_THETA, A_H2O = 11 + L };
   gbl_float *A = acc;
@@ -2354,6 +2405,7 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
 #pragma unroll
     for (int k = 0; k < 12 + L; k++)
       if (later(k)) A[k * as] = a[k];
+    mo.template day_end<L>(day, nt, A, as, rnf_sum);
   }
   // :263-290
   if (!act) return 0;

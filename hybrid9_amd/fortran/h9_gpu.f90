@@ -15,6 +15,7 @@ IMPLICIT NONE
 INTEGER, PARAMETER :: H9G_LMAX = 10
 INTEGER, PARAMETER :: H9G_NDIAG = 12
 INTEGER, PARAMETER :: H9G_NDAILY = 11
+INTEGER, PARAMETER :: H9G_NMONTHS = 12
 INTEGER, PARAMETER :: H9G_ERR_TRIDIAG1 = 1, H9G_ERR_TRIDIAG2 = 2
 INTEGER, PARAMETER :: H9G_ERR_RSUB_POS = 3, H9G_ERR_IMBALANCE = 4
 INTEGER, PARAMETER :: H9G_ERR_NOSNAP = 5   ! internal invariant, not a reference STOP
@@ -339,6 +340,33 @@ INTERFACE
     INTEGER(C_INT), VALUE :: k
     REAL(C_FLOAT) :: out (*)
     INTEGER(C_INT) :: h9g_get_daily
+  END FUNCTION
+  ! Monthly output: on /= 0 makes later runs record the year's 12+L running
+  ! sums at every month end (the monthly year kernels); 0 (default) turns it off.
+  FUNCTION h9g_set_monthly (ctx, on) BIND(C, NAME='h9g_set_monthly')
+    IMPORT :: C_PTR, C_INT
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: on
+    INTEGER(C_INT) :: h9g_set_monthly
+  END FUNCTION
+  ! The snapshots of year k (0-based) of the last run: out (ncell, 12+L, 12).
+  FUNCTION h9g_get_monthly (ctx, k, out) BIND(C, NAME='h9g_get_monthly')
+    IMPORT :: C_PTR, C_INT, C_FLOAT
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: k
+    REAL(C_FLOAT) :: out (*)
+    INTEGER(C_INT) :: h9g_get_monthly
+  END FUNCTION
+  ! Monthly means of year jyear from its snapshots (ncell, 12+L, 12) to
+  ! mxyYYYY.nc: the fields of h9g_write_axy_nc under a leading dimension month.
+  FUNCTION h9g_write_mxy_nc (path, nx, ny, nlayers, zc, ncell, gid, jyear, nisurf, snapshots) &
+      BIND(C, NAME='h9g_write_mxy_nc')
+    IMPORT :: C_INT, C_CHAR, C_FLOAT, C_INT64_T
+    CHARACTER(KIND=C_CHAR), INTENT(IN) :: path (*)
+    INTEGER(C_INT), VALUE :: nx, ny, nlayers, ncell, jyear, nisurf
+    REAL(C_FLOAT), INTENT(IN) :: zc (*), snapshots (*)
+    INTEGER(C_INT64_T), INTENT(IN) :: gid (*)
+    INTEGER(C_INT) :: h9g_write_mxy_nc
   END FUNCTION
   FUNCTION h9g_last_kernel_ms (ctx) BIND(C, NAME='h9g_last_kernel_ms')
     IMPORT :: C_PTR, C_FLOAT

@@ -43,6 +43,13 @@ PROGRAM H9_HOST
 ! LCLIM/daily_diag.csv is written under the working directory with the
 ! reference's header, format and order (decade, cell, year, day).
 !
+! monthly = 1 records every year kernel's month-end running sums
+! (h9g_set_monthly, DESIGN.md §7) and writes each year's monthly means to
+! <out_dir>/mxyYYYY.nc (h9g_write_mxy_nc: axyYYYY.nc's fields under a leading
+! dimension month), in both cell_order settings; ordered_decades is left as
+! given (the decades stay overlapped).  On a grid the cells sit at their grid
+! ids; a case's cells form a grid of one row, in their order.
+!
 ! Usage:  h9_host [driver.txt] [h9gpu.nml]
 ! Outputs: <out_dir>/annual.f32 (ncell, 12+L, nyears),
 !          <out_dir>/state_end.f32 (packed state, include/h9g.h) and, on a
@@ -63,11 +70,11 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 ! --- extension namelist ----------------------------------------------------
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
-INTEGER :: cell_order, ordered_decades, daily
+INTEGER :: cell_order, ordered_decades, daily, monthly
 INTEGER(C_INT64_T) :: seed
 NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
-                 cell_order, ordered_decades, daily
+                 cell_order, ordered_decades, daily, monthly
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
 TYPE(C_PTR) :: pgf_ptr (7)
 CHARACTER (LEN = *), PARAMETER :: pgf_var (7) = &
@@ -101,6 +108,10 @@ REAL(C_FLOAT), ALLOCATABLE :: dbuf (:,:,:)
 INTEGER, ALLOCATABLE :: dyear (:)
 INTEGER :: dfill, dnyr, udaily, ucsv, lon_s_w, lat_s_w, nwin, ix, iy
 REAL :: a_lon, b_lon, a_lat, b_lat, lon1, lat1
+! --- monthly output (h9g_set_monthly): a year's snapshots and its grid ------
+REAL(C_FLOAT), ALLOCATABLE :: mon (:,:,:)
+INTEGER(C_INT64_T), ALLOCATABLE :: mgid (:)
+INTEGER :: mnx, mny
 
 !----------------------------------------------------------------------!
 ! Defaults, then driver.txt and h9gpu.nml.
@@ -108,6 +119,7 @@ REAL :: a_lon, b_lon, a_lat, b_lat, lon1, lat1
 input_mode = 'synth'; case_dir = ''; out_dir = '.'; pgf_dir = '.'
 nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
+monthly = 0
 daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
 PATH_output = '.'
 seed = 20161123_C_INT64_T
@@ -299,6 +311,19 @@ IF (daily /= 0) THEN
                   &  theta_ma_1,  lai,  lai_litter, w_i, fT'
   END IF
 END IF
+IF (monthly /= 0) THEN
+  CALL chk (h9g_set_monthly (ctx, 1))
+  ALLOCATE (mon (ncell, 12 + L, H9G_NMONTHS), mgid (ncell))
+  IF (TRIM (input_mode) == 'case') THEN
+    mnx = ncell; mny = 1
+    DO i = 1, ncell
+      mgid (i) = i - 1
+    END DO
+  ELSE
+    mnx = nx; mny = ny
+    mgid = gid (1:ncell)
+  END IF
+END IF
 d0 = 1
 IF (cell_order /= 0) THEN
   ! HYBRID9.f90:93-130: decade by decade (1901-1910, 1911-1920, ...), cut to
@@ -339,6 +364,7 @@ IF (cell_order /= 0) THEN
     DO k = 1, iyr
       annual = annual_dec (:, :, k)
       CALL year_out (dsyr + k - 1)
+      IF (monthly /= 0) CALL month_out (k - 1, dsyr + k - 1)
     END DO
     CALL h9g_check_stop (ctx, rc)
     WRITE (*,'(A,I5,A,I5,A,12I3)') ' years', dsyr, ' -', deyr, ' in cell order: passes per decade', &
@@ -356,6 +382,7 @@ DO iyr = 1, nyears
   CALL h9g_check_stop (ctx, rc)
   CALL chk (h9g_get_annual (ctx, annual))
   CALL year_out (jyear)
+  IF (monthly /= 0) CALL month_out (0, jyear)
   IF (daily /= 0) THEN                       ! flushed at the end of each reference decade
     CALL daily_year (0, jyear)
     IF (MODULO (jyear - 1900, 10) == 0 .OR. iyr == nyears) CALL daily_flush ()
@@ -393,6 +420,16 @@ CONTAINS
           ' mean runoff', diag (2) / MAX (diag (1), 1.0D0), ' mm/s  mean soil water', &
           diag (3) / MAX (diag (1), 1.0D0), ' mm  (', h9g_last_kernel_ms (ctx), ' ms)'
   END SUBROUTINE year_out
+
+  ! The month-end snapshots of year k (0-based) of the last run, calendar
+  ! year y, as monthly means to <out_dir>/mxyYYYY.nc.
+  SUBROUTINE month_out (k, y)
+    INTEGER, INTENT(IN) :: k, y
+    CALL chk (h9g_get_monthly (ctx, k, mon))
+    WRITE (ydate,'(I4)') y
+    CALL chk (h9g_write_mxy_nc (TRIM (out_dir)//'/mxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, L, zc, ncell, &
+                                mgid, y, NISURF, mon))
+  END SUBROUTINE month_out
 
   ! The daily lines of year k (0-based) of the last run, calendar year y,
   ! appended to the current decade's.

@@ -253,6 +253,40 @@ int h9g_set_daily(h9g_ctx *ctx, int nsel, const int32_t *cells);
  * H9G_EINVAL for a bad k. */
 int h9g_get_daily(h9g_ctx *ctx, int k, float *out);
 
+/* --- monthly output: month-end running sums from the year kernels ------- */
+/* The reference writes one mean per cell and year.  With monthly recording
+ * on, every year kernel also stores, at the end of each calendar month's
+ * last day (INIT.f90:844-859: day 31, 59, 90, ... 365, one later from
+ * February on in a year of 366 days), the year's 12+L running sums as they
+ * then stand: after GROW and the additions of HYBRID9.f90:235-254,
+ * undivided, in h9g_get_annual's row order --
+ *   npp_sum plant_mass_sum rnf_sum 0 tas..rhs sums theta_sum(1..L)
+ *   h2osoi_sum_total
+ * (row evap is the reference's zero: it never accumulates evap_sum).  The
+ * sums are never reset, so the annual means stay the reference's; snapshot
+ * 11 is the year's final sums, and divided as :263-290 divides them it gives
+ * the annual means bit for bit.  A snapshot is a prefix of the reference's
+ * own f32 summation.  The mean of month m is derived on the host from two
+ * snapshots, in double: (S[m] - S[m-1]) / days_m  (S[-1] = 0; divisor
+ * days_m * nisurf for rnf, 1 for npp, a monthly total): deterministic, but
+ * derived from f32 running sums, not a reference quantity.
+ * A cell that reaches a reference STOP in a year has NaN in all twelve
+ * months of that year and of every later one; a masked cell, or one that
+ * had stopped before the run, throughout.
+ * Monthly kernels are the year kernels under other names; with recording off
+ * (the default) not one launch, allocation or synchronisation is added, and
+ * annual means, state, STOP records and daily lines are the same bit for bit
+ * either way.  The snapshots take nyears x 12 x (12+L) x ncell floats of
+ * device memory per call (1.3 GB for 20 years of the 0.5 deg grid), allocated
+ * by the run and released with the context (not part of h9g_config_bytes). */
+#define H9G_NMONTHS 12
+int h9g_set_monthly(h9g_ctx *ctx, int on);
+/* Snapshots of year k (0-based) of the last h9g_run_year (k = 0),
+ * h9g_run_decade_ordered or h9g_run_ordered call: out (12, 12+L, ncell),
+ * cell fastest.  Synchronises.  H9G_ESTATE if nothing was recorded,
+ * H9G_EINVAL for a bad k. */
+int h9g_get_monthly(h9g_ctx *ctx, int k, float *out);
+
 /* --- outputs (HYBRID9.f90:263-290) ------------------------------------ */
 /* Annual means of the last year run, (12+L) rows of (ncell):
  * npp plant_mass rnf evap tas rlds rsds huss ps pr rhs theta(1..L)
@@ -290,6 +324,14 @@ int h9g_synth_forcing(h9g_ctx *ctx, int slot, uint64_t seed, int day0,
 int h9g_write_axy_nc(const char *path, int nx, int ny, int nlayers,
                      const float *zc, int ncell, const int64_t *gid,
                      const float *annual);
+/* mxyYYYY.nc: the monthly means of year jyear derived from its month-end
+ * snapshots (h9g_get_monthly, (12, 12+L, ncell)) as described there, with
+ * axyYYYY.nc's variables, names, units and NaN fill under a leading
+ * dimension `month` of 12; net primary production in g[DM]/m^2/month.
+ * CDF-2.  Host only. */
+int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers,
+                     const float *zc, int ncell, const int64_t *gid, int jyear,
+                     int nisurf, const float *snapshots);
 /* READ_PGF.f90 / READ_NET_CDF_3DR.f90: days [t0, t0+nt) of variable 4
  * (time, lat, lon) of the 7 PGF files (tas rlds rsds huss ps pr rhs)
  * gathered at the grid ids gid into out (7, nt, ncell).  Host only. */

@@ -32,15 +32,24 @@ LLVM = Path("/opt/rocm/lib/llvm/bin")
 
 
 def disassemble(so: Path) -> str:
+    """Every device unit's code object (.hip_fatbin holds one offload bundle
+    per translation unit, one after the other)."""
     with tempfile.TemporaryDirectory() as d:
-        fat, co = Path(d) / "fat.bin", Path(d) / "co.elf"
+        fat = Path(d) / "fat.bin"
         subprocess.run(["objcopy", f"--dump-section=.hip_fatbin={fat}", str(so), str(Path(d) / "x.so")],
                        check=True, capture_output=True)
-        subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True,
-                       capture_output=True)
-        return subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], check=True,
-                              capture_output=True, text=True).stdout
+        data = fat.read_bytes()
+        starts = [m.start() for m in re.finditer(rb"__CLANG_OFFLOAD_BUNDLE__", data)] or [0]
+        out = []
+        for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+            part, co = Path(d) / f"fat{i}.bin", Path(d) / f"co{i}.elf"
+            part.write_bytes(data[a:b])
+            subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True,
+                           capture_output=True)
+            out.append(subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], check=True,
+                                      capture_output=True, text=True).stdout)
+        return "\n".join(out)
 
 
 def calls_per_function(so: Path) -> dict:

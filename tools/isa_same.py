@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Are two builds' kernels the same machine code?
 
-    python tools/isa_same.py A B [--only REGEX]
+    python tools/isa_same.py A B [--only REGEX] [--common]
 
 A and B are each a device assembly (hipcc --cuda-device-only -S), a
 disassembly (llvm-objdump -d of a gfx950 code object), or a built library /
@@ -15,7 +15,8 @@ and a line-by-line pass says whether they differ in literal operands alone
 (a pc-relative literal of a disassembly moves with the layout).  Every
 kernel's metadata (VGPR, AGPR, SGPR, both spill counts, private and LDS
 bytes) is compared where the input carries it.  Exit status 0 when every
-kernel common to both is identical in text and metadata and none is missing.
+kernel common to both is identical in text and metadata and none is missing
+(--common: kernels in one build only are listed but do not fail it).
 The comparison is generic: no instruction is looked for by name."""
 from __future__ import annotations
 
@@ -110,17 +111,21 @@ def load(path: Path):
     """(kernel -> instruction lines, kernel -> metadata or {})"""
     head = path.read_bytes()[:4]
     if head == b"\x7fELF":
+        ks, meta = {}, {}
         with tempfile.TemporaryDirectory() as t:
-            co = path
+            cos = [path]
             secs = subprocess.run([str(kernel_meta.LLVM / "llvm-readelf"), "-S", "-W", str(path)],
                                   capture_output=True, text=True, check=True).stdout
-            if ".hip_fatbin" in secs:
-                co = kernel_meta.code_object(path, Path(t))
-            dis = subprocess.run([str(kernel_meta.LLVM / "llvm-objdump"), "-d", str(co)], capture_output=True,
-                                 text=True, check=True).stdout
-            notes = subprocess.run([str(kernel_meta.LLVM / "llvm-readelf"), "--notes", str(co)],
-                                   capture_output=True, text=True, check=True).stdout
-        return kernels_of_dis(dis), parse_meta(notes)
+            if ".hip_fatbin" in secs:       # a library: every device unit's code object
+                cos = kernel_meta.code_objects(path, Path(t))
+            for co in cos:
+                dis = subprocess.run([str(kernel_meta.LLVM / "llvm-objdump"), "-d", str(co)], capture_output=True,
+                                     text=True, check=True).stdout
+                notes = subprocess.run([str(kernel_meta.LLVM / "llvm-readelf"), "--notes", str(co)],
+                                       capture_output=True, text=True, check=True).stdout
+                ks.update(kernels_of_dis(dis))
+                meta.update(parse_meta(notes))
+        return ks, meta
     text = path.read_text(errors="replace")
     if re.search(r"^[0-9a-f]+ <[^>]+>:", text, re.M):
         return kernels_of_dis(text), parse_meta(text)
@@ -205,6 +210,9 @@ def main() -> int:
             print(f"    opcode counts{' (encodings folded)' if fold else ''}: " +
                   (", ".join(f"{k} {ca[k]} -> {cb[k]}" for k in sorted(d)) or "equal"))
     print(f"{same} identical, {diff} not")
+    if "--common" in sys.argv:      # a build that adds kernels: those of both must be the same
+        missing = sum(1 for n in names if n not in ka or n not in kb)
+        return 0 if diff == missing else 1
     return 0 if diff == 0 else 1
 
 

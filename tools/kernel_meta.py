@@ -8,7 +8,8 @@ Extracts the .hip_fatbin section, unbundles the gfx950 code object with
 clang-offload-bundler and reads the AMDHSA metadata note with llvm-readelf:
 VGPRs, AGPRs, SGPRs, spilled VGPRs/SGPRs, private (scratch) bytes per lane
 and static LDS bytes per workgroup.  Without --all only the year kernels
-(pair, pair2, solo) are printed."""
+(pair, pair2, solo) and their monthly siblings (*_mon_kernel, listed beside
+them) are printed."""
 from __future__ import annotations
 
 import re
@@ -21,14 +22,31 @@ LLVM = Path("/opt/rocm/lib/llvm/bin")
 ROOT = Path(__file__).resolve().parents[1]
 
 
-def code_object(lib: Path, tmp: Path) -> Path:
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def code_objects(lib: Path, tmp: Path) -> list[Path]:
+    """The gfx950 code object of every device translation unit of the library
+    (the year kernels' and the monthly kernels'): .hip_fatbin holds one
+    offload bundle per unit, one after the other."""
     fat = tmp / "fat.bin"
     subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib), str(tmp / "x.so")],
                    check=True)
-    co = tmp / "gfx950.co"
-    subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
-                    f"--output={co}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
-    return co
+    data = fat.read_bytes()
+    starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), data)] or [0]
+    out = []
+    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+        part, co = tmp / f"fat{i}.bin", tmp / f"gfx950_{i}.co"
+        part.write_bytes(data[a:b])
+        subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}",
+                        f"--output={co}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
+        out.append(co)
+    return out
+
+
+def code_object(lib: Path, tmp: Path) -> Path:
+    """The first unit's (h9g.hip: every kernel but the monthly ones)."""
+    return code_objects(lib, tmp)[0]
 
 
 def kernels(co: Path) -> list[dict]:
@@ -76,14 +94,16 @@ def main() -> None:
     pos = [a for a in sys.argv[1:] if not a.startswith("--")]
     lib = Path(pos[0]) if pos else ROOT / "hybrid9_amd" / "lib" / "libh9g.so"
     with tempfile.TemporaryDirectory() as t:
-        co = code_object(lib, Path(t))
-        ks, sizes = kernels(co), code_sizes(co)
+        ks, sizes = [], {}
+        for co in code_objects(lib, Path(t)):
+            ks += kernels(co)
+            sizes.update(code_sizes(co))
     names = demangle([k["name"] for k in ks])
     print(f"{lib.name}: {len(ks)} kernels")
     print(f"{'kernel':60s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'VGPR spill':>10s} {'SGPR spill':>10s} "
           f"{'private B':>9s} {'LDS B':>7s} {'code B':>7s}")
     for k, nm in sorted(zip(ks, names), key=lambda x: x[1]):
-        if "--all" not in sys.argv and not re.search(r"h9g_(pair|pair1|pair2|pair11|solo)_kernel", nm):
+        if "--all" not in sys.argv and not re.search(r"h9g_(pair|pair1|pair2|pair11|solo)(_mon)?_kernel", nm):
             continue
         short = nm.replace("h9k::", "").replace("(KArgs, ", "(")
         print(f"{short[:60]:60s} {k.get('vgpr', 0):5d} {k.get('agpr', 0):5d} {k.get('sgpr', 0):5d} "
