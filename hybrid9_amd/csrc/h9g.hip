@@ -140,12 +140,17 @@ constexpr int pair_waves() { return pair_resident<L>(); }
 // (h9g_pair11_kernel: 42 helper lanes, 2 rounds per phase at L = 10).
 // MON: the monthly kernels (month-end snapshots of the running sums into
 // `mon`, addressed as a.annual: 12 * annual rows per cell).
-template <int L, class G, int R, int C = H9G_PCPW, bool MON = false>
+// FRONT: the one-column kernel's two-wave shape (h9g_pair.h front_year_pair):
+// a workgroup is one column, wave 0 its main wave and wave 1 its front wave,
+// both on the column's one LDS block.
+template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT = false>
 __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr) {
-  typedef PairStore<L, 2 * C, R> PS;
+  typedef PairStore<L, 2 * C, R, FRONT ? 1 : 0> PS;
+  static_assert(!FRONT || C == 1, "the front wave serves a one-column wave");
+  constexpr int NW = FRONT ? 1 : H9G_PWAVES;               // column blocks per workgroup
   __shared__ uint64_t s_e2[32];
   __shared__ double s_l2[32];
-  __shared__ float s_cell[H9G_PWAVES][PS::ROWS * 2 * C];   // [wave][row][lane]
+  __shared__ float s_cell[NW][PS::ROWS * 2 * C];           // [wave][row][lane]
   __shared__ float s_zt[zt_size<L>()];
   // the day snapshot addresses its global block by LDS byte offset
   // (PairStore::svw): every static LDS address must lie inside GBLOCK
@@ -154,7 +159,19 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
   if (threadIdx.x == 0) fill_zt<L>(g, s_zt);
   load_tabs(s_e2, s_l2);
   const h9m::Tabs T = {s_e2, s_l2};
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wave = FRONT ? 0 : threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // the front wave runs everything down to the year like the main wave: the
+  // same early returns from the same values, and the same values stored to the
+  // same words of the block (so it waits for nothing before its first barrier).
+  // The reverse must hold too: a front-wave store that lands late must not hit
+  // a word the main wave has rewritten meanwhile.  The prologue stores the
+  // parameter slots PF_TS..PF_PSI, PS_FMAX, PF_ROOTR and cell_inv_pair's fields
+  // (PF_NINVB..PF_RTS1, PS_MH3, PS_TSDZ1); before the first barrier 1 the main
+  // wave writes only park's plant state (PS_LAI..), day_consts' PS_DAY and
+  // PS_DR* and the HO_* words, and rootr not before the first day's end, many
+  // barriers later: the two sets are disjoint.  A field added to either side
+  // has to keep them so.
+  const bool front_wave = FRONT && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;
   // lanes 0..43: 22 pairs; 44..63: spare lanes, which join the pairs only in
   // the per-layer phases (Split2, hydrology_pair).  Spare lane 44 + j mirrors
   // pair lane 12 + j (mod the wave's pair lanes): its LDS column and
@@ -167,7 +184,7 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
   if (spare && !PS::kSpare) return;
   const int h = lane & 1;
   const int slot0 = __builtin_amdgcn_readfirstlane(
-      a.c0 + (int)(xcd_vwg(blockIdx.x, gridDim.x) * H9G_PWAVES + wave) * C);
+      a.c0 + (int)(xcd_vwg(blockIdx.x, gridDim.x) * NW + wave) * C);
   // the wave's group (wave-uniform: split is a multiple of C)
   const bool g2 = slot0 >= a.split;
   const int lim = g2 ? a.cend : a.bend;
@@ -214,14 +231,27 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
   if (!spare) {
     H9K_TS_SUM(L, cs, ts_sum)
     if (!(ts_sum > SOIL_TRUNC) || err[c] != 0) {
-      if (h == 0) nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
+      if (h == 0 && !front_wave) nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
       if constexpr (MON)
-        if (h == 0) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
+        if (h == 0 && !front_wave) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
       return;
     }
     cell_inv_pair<L, G>(g, cs);
   }
   if (__builtin_amdgcn_ballot_w64(!spare) == 0) return;   // every pair masked out: the spare lanes leave too
+  if constexpr (FRONT) {
+    if (front_wave) {
+#if defined(H9G_STAMPS)
+      StampProf fp{stamp_clock(), {0, 0, 0, 0, 0, 0, 0, 0}};
+      front_year_pair<L, G>(g, cs, sp, T, fp);
+      if (lane == 0 && a.stamps)            // the front waves' records follow the main waves'
+        for (int k = 0; k < 8; k++) a.stamps[(gridDim.x + blockIdx.x) * 8 + k] = fp.acc[k];
+#else
+      front_year_pair<L, G>(g, cs, sp, T);
+#endif
+      return;
+    }
+  }
   int eday = 0, estep = 0;
   float errval = 0.0f;
 #if defined(H9G_STAMPS)
@@ -230,7 +260,7 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
                                                          a.nisurf, a.grow_on, (gbl_float *)(a.annual + io), ios, eday,
                                                          estep, errval, T, a.raw, pr);
   if (lane == 0 && a.stamps)
-    for (int k = 0; k < 8; k++) a.stamps[(blockIdx.x * H9G_PWAVES + wave) * 8 + k] = pr.acc[k];
+    for (int k = 0; k < 8; k++) a.stamps[(blockIdx.x * NW + wave) * 8 + k] = pr.acc[k];
 #else
   int code;
   if constexpr (MON)
@@ -301,6 +331,19 @@ __global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_p
 h9g_pair1_kernel(const KArgs a, const G g) {
   pair_body<L, G, 1, 1>(a, g);
 }
+// Its two-wave shape (round 9): a workgroup is one column, whose second wave
+// evaluates the front of each substep beside the first wave's per-layer rounds
+// (h9g_pair.h front_year_pair).  Twice the waves per cell, one per SIMD still:
+// for lists of at most H9G_PAIR1_FRONT_MAX cells (pair1_front); longer lists
+// keep the single-wave kernel above.  Both run as kind K_PAIR1.
+#define H9G_PAIR1_FRONT_MAX 512
+#if H9G_P1_FRONT
+template <int L, class G>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
+h9g_pair1f_kernel(const KArgs a, const G g) {
+  pair_body<L, G, 1, 1, false, true>(a, g);
+}
+#endif
 
 
 // Solo kernel: one lane per soil column running the generic code of
@@ -394,6 +437,13 @@ __global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_p
 h9g_pair1_mon_kernel(const KArgs a, float *mon, const G g) {
   pair_body<L, G, 1, 1, true>(a, g, mon);
 }
+#if H9G_P1_FRONT
+template <int L, class G>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
+h9g_pair1f_mon_kernel(const KArgs a, float *mon, const G g) {
+  pair_body<L, G, 1, 1, true, true>(a, g, mon);
+}
+#endif
 template <int L, class G>
 __global__ void __launch_bounds__(H9G_YBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 h9g_solo_mon_kernel(const KArgs a, float *mon, const G g) {
@@ -404,8 +454,8 @@ h9g_solo_mon_kernel(const KArgs a, float *mon, const G g) {
 // (h9g_mon.hip: this file with H9G_MONTHLY_UNIT, which keeps the year
 // kernels' code above, the kernel kinds and the geometry dispatch below, and
 // h9g_mon_launch), beside this one, so the two build at the same time.
-int h9g_mon_launch(int kind, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream, const KArgs &a,
-                   float *mon);
+int h9g_mon_launch(int kind, bool p1f, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream,
+                   const KArgs &a, float *mon);
 int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);
 
 #if !defined(H9G_MONTHLY_UNIT)
@@ -1115,6 +1165,17 @@ static constexpr KindInfo kind_info(int kind) {
   }
 }
 
+// The one-column kernel runs a launch of at most H9G_PAIR1_FRONT_MAX cells in
+// its two-wave shape, a workgroup per cell (h9g_pair1f_kernel: still at most
+// one wave per SIMD).  Decided by the launch's cells alone.
+static bool pair1_front(size_t cells) { return H9G_P1_FRONT && cells <= H9G_PAIR1_FRONT_MAX; }
+// Cells per workgroup of a launch of `kind`; p1f: in the one-column kernel's
+// two-wave shape.  run_year_impl decides p1f once per launch, from the
+// launch's cells, and hands it to everything that depends on the shape: the
+// sort's and the forcing gather's traversal, the grid, launch_year's block
+// size and kernel, the monthly dispatch, the name of the kernel that ran.
+static int launch_block_cells(int kind, bool p1f) { return p1f ? 1 : kind_info(kind).block_cells; }
+
 struct h9g_ctx {
   h9g_config cfg;
   int device = 0;
@@ -1136,7 +1197,7 @@ struct h9g_ctx {
   int last_year = 0;
   int params_set = 0, state_set = 0, ran = 0;
   h9g_error last_err{};
-  std::string kname;
+  std::string kname, targs;       // the year kernel's name; its template arguments
   unsigned *d_stamps = nullptr;   // H9G_STAMPS builds only
   std::vector<int64_t> h_gid;     // grid ids of the cells (h9g_set_cells), for NetCDF ingest
   std::vector<float *> h_pin;     // per-slot pinned staging of the NetCDF prefetch
@@ -1167,6 +1228,8 @@ struct h9g_ctx {
   size_t n_solo = 0;   // K_MIXED: cells [0, n_solo) run on the solo kernel, the rest on the pair kernel
   size_t ios = 0;      // slots of the slot-ordered buffers (d_perm, d_forc_s, d_ann_s): twice the cells
   size_t stamp_words = 0;
+  bool stamp_p1f = false;         // the last stamped launch: run_year_impl's shape decision ...
+  size_t stamp_blocks = 0;        // ... and its grid (the front waves' records follow the grid's main waves')
   int ev_kind[NEVT] = {};         // kernel kind and cell-years of each timed launch
   int64_t ev_cells[NEVT] = {};
   double kstat[K_NSTAT][3] = {};        // per kernel kind: launches, cell-years, ms (h9g_launch_stats)
@@ -1194,6 +1257,11 @@ struct h9g_ctx {
   int mon_years = 0;              // years recorded by the last call (0: none)
   bool mon_in_ret = false;        // ... in d_mon_ret (an ordered call) or d_mon (h9g_run_year)
 };
+
+// The one-column kernel's name by shape (p1f: the two-wave shape).
+static std::string pair1_name(const h9g_ctx *ctx, bool p1f) {
+  return std::string("h9g_pair1") + (p1f ? "f" : "") + "_kernel" + ctx->targs;
+}
 
 static void ord_free(h9g_ctx *ctx);
 
@@ -1312,8 +1380,9 @@ int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t st
 
 // The monthly kernel of a launch of `kind` (not K_MIXED: launch_year cuts
 // that into its two parts) with the configuration's geometry variant.
-int h9g_mon_launch(int kind, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream, const KArgs &a,
-                   float *mon) {
+// p1f: the one-column kernel's two-wave shape (run_year_impl's decision).
+int h9g_mon_launch(int kind, bool p1f, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream,
+                   const KArgs &a, float *mon) {
   const struct { int L; h9g_config cfg; } c{cfg->nlayers, *cfg};
   switch (kind) {
     case K_SOLO: H9G_DISPATCH(&c, h9g_solo_mon_kernel, grid, block, stream, a, mon); break;
@@ -1322,7 +1391,15 @@ int h9g_mon_launch(int kind, const h9g_config *cfg, unsigned grid, unsigned bloc
       H9G_DISPATCH_L10(&c, h9g_pair2_mon_kernel, grid, block, stream, a, mon);
       break;
     case K_PAIR11: H9G_DISPATCH(&c, h9g_pair11_mon_kernel, grid, block, stream, a, mon); break;
-    case K_PAIR1: H9G_DISPATCH(&c, h9g_pair1_mon_kernel, grid, block, stream, a, mon); break;
+    case K_PAIR1:
+#if H9G_P1_FRONT
+      if (p1f) {
+        H9G_DISPATCH(&c, h9g_pair1f_mon_kernel, grid, block, stream, a, mon);
+        break;
+      }
+#endif
+      H9G_DISPATCH(&c, h9g_pair1_mon_kernel, grid, block, stream, a, mon);
+      break;
     case K_PAIR: H9G_DISPATCH(&c, h9g_pair_mon_kernel, grid, block, stream, a, mon); break;
     default: return H9G_EINVAL;
   }
@@ -1441,8 +1518,9 @@ size_t h9g_config_bytes(const h9g_config *cfg) {
   const size_t ios = 2 * round_up(n, H9G_PCPW) + 64;
   // the largest launch's day-snapshot blocks: the 11-column kernel's over
   // every cell, or the one-column kernel's over H9G_PAIR1_MAX listed cells
+  // (a workgroup per cell up to H9G_PAIR1_FRONT_MAX)
   const size_t blocks = std::max((ios + (size_t)H9G_PCPW11 * H9G_PWAVES - 1) / ((size_t)H9G_PCPW11 * H9G_PWAVES),
-                                 (size_t)1024 / H9G_PWAVES);
+                                 std::max((size_t)1024 / H9G_PWAVES, (size_t)H9G_PAIR1_FRONT_MAX));
   // + the slot-ordered copies of a forcing slot and of the annual sums
   // (h9g_run_year, allocated on first use), the ordered mode's decade
   // buffers (h9g_run_ordered, decades of up to 10 years)
@@ -1600,7 +1678,11 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
   const GeoKind gk = geo_kind(*cfg);
   const std::string targs = "<" + std::to_string(L) + "," +
                             (gk == GEO_R ? "GeoR" : "GeoC<" + std::to_string(L) + "," + std::to_string((int)gk) + ">") + ">";
-  auto kernel_name = [&](int k) { return "h9g_" + std::string(kind_info(k).env) + "_kernel" + targs; };
+  ctx->targs = targs;
+  // (a one-column context of few cells runs every year in the two-wave shape)
+  auto kernel_name = [&](int k) {
+    return k == K_PAIR1 ? pair1_name(ctx, pair1_front(ctx->n)) : "h9g_" + std::string(kind_info(k).env) + "_kernel" + targs;
+  };
   ctx->kname = ctx->kind == K_MIXED ? kernel_name(K_SOLO) + "+" + kernel_name(K_PAIR) : kernel_name(ctx->kind);
   return ctx;
 }
@@ -1827,7 +1909,9 @@ static Kind list_kind(const h9g_ctx *ctx, int m) {
 // [0, n_solo) in solo blocks and [n_solo, n) in pair blocks.
 struct LaunchRange { int c0, cend, cpb; Kind kind; };
 static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
-  const int n = (int)ctx->n, ns = (int)ctx->n_solo, cpb = kind_info(ctx->kind).block_cells;
+  // (an every-cell launch: run_year_impl's decision for the context's n cells)
+  const int n = (int)ctx->n, ns = (int)ctx->n_solo;
+  const int cpb = launch_block_cells(ctx->kind, ctx->kind == K_PAIR1 && pair1_front(ctx->n));
   int k = 0;
   if (ctx->kind != K_MIXED) {
     r[k++] = {0, n, cpb, ctx->kind};
@@ -1841,11 +1925,13 @@ static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
 // The year kernel of a launch of `kind` over a's slots: `blocks` workgroups
 // of its pair part; the mixed kind over year_ranges' two.
 // mon: the base of the launch's monthly rows; then the kind's monthly kernel.
-static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks, float *mon) {
-  const unsigned pb = (unsigned)blocks, pt = 64 * H9G_PWAVES;
+// p1f (K_PAIR1 only): the two-wave shape, workgroups of two waves and `blocks`
+// of one cell each.
+static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks, float *mon, bool p1f) {
+  const unsigned pb = (unsigned)blocks, pt = p1f ? 128 : 64 * H9G_PWAVES;
   if (mon && kind != K_MIXED) {
     const bool solo = kind == K_SOLO;
-    if (int rc = h9g_mon_launch(kind, &ctx->cfg, solo ? (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK) : pb,
+    if (int rc = h9g_mon_launch(kind, p1f, &ctx->cfg, solo ? (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK) : pb,
                                 solo ? H9G_YBLOCK : pt, ctx->sc, a, mon))
       return rc;
     HIPCHK(hipGetLastError());
@@ -1862,13 +1948,21 @@ static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks, float *mo
       for (int i = 0; i < nr; i++) {
         a.c0 = r[i].c0;
         a.cend = a.bend = a.split = r[i].cend;
-        if (int rc = launch_year(ctx, r[i].kind, a, blocks, mon)) return rc;
+        if (int rc = launch_year(ctx, r[i].kind, a, blocks, mon, false)) return rc;
       }
       return 0;
     }
     case K_PAIR2: H9G_DISPATCH_L10(ctx, h9g_pair2_kernel, pb, pt, ctx->sc, a); break;
     case K_PAIR11: H9G_DISPATCH(ctx, h9g_pair11_kernel, pb, pt, ctx->sc, a); break;
-    case K_PAIR1: H9G_DISPATCH(ctx, h9g_pair1_kernel, pb, pt, ctx->sc, a); break;
+    case K_PAIR1:
+#if H9G_P1_FRONT
+      if (p1f) {
+        H9G_DISPATCH(ctx, h9g_pair1f_kernel, pb, pt, ctx->sc, a);
+        break;
+      }
+#endif
+      H9G_DISPATCH(ctx, h9g_pair1_kernel, pb, pt, ctx->sc, a);
+      break;
     default: H9G_DISPATCH(ctx, h9g_pair_kernel, pb, pt, ctx->sc, a); break;
   }
   HIPCHK(hipGetLastError());
@@ -1937,6 +2031,8 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   const Kind kind = d_list && !ys.bulk ? list_kind(ctx, m) : ctx->kind;
   const KindInfo ki = kind_info(kind);
   const size_t ncells = d_list ? (size_t)m : ctx->n;
+  // the launch's shape, decided here once (the one-column kernel carries no second group: ncells is the launch)
+  const bool p1f = kind == K_PAIR1 && pair1_front(ncells);
   // slot-ordered forcing and annual sums (row stride ios: the cells plus a
   // second group's slack)
   if (d_list || ctx->sort) {
@@ -1965,7 +2061,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     return 0;
   };
   if (d_list) {
-    const int pcpb = ki.block_cells;
+    const int pcpb = launch_block_cells(kind, p1f);
     a.perm = d_list;
     if (ctx->sort && kind != K_PAIR1) {
       // the list in h9g_sort_kernel's order (its waves' columns take the
@@ -2008,7 +2104,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   // the monthly rows, addressed as a.annual
   float *const mon_a = !mon ? nullptr : a.sorted_io ? ctx->d_mon_s : ctx->d_mon;
   // workgroups of the launch (the pair part's, for the mixed kind)
-  const size_t per_block = (size_t)ki.block_cells;
+  const size_t per_block = (size_t)launch_block_cells(kind, p1f);
   const size_t blocks = kind == K_MIXED ? (ctx->n - ctx->n_solo + per_block - 1) / per_block
                                         : ((size_t)a.cend + per_block - 1) / per_block;
   if (ki.pair) {
@@ -2042,6 +2138,8 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     }
     HIPCHK(hipMemsetAsync(ctx->d_stamps, 0, sizeof(unsigned) * words, ctx->sc));
     a.stamps = ctx->d_stamps;
+    ctx->stamp_p1f = p1f;
+    ctx->stamp_blocks = blocks;
   }
 #endif
   if (ctx->nev >= NEVT)   // fold finished timings before reusing events
@@ -2073,7 +2171,10 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   ctx->ev_kind[e] = ys.probe ? K_PROBE : kind;
   ctx->ev_cells[e] = (int64_t)ncells + (two ? ys.k2 : 0);
   HIPCHK(hipEventRecord(ctx->ev0[e], ctx->sc));
-  if (int r = launch_year(ctx, kind, a, blocks, mon_a)) return r;
+  if (int r = launch_year(ctx, kind, a, blocks, mon_a, p1f)) return r;
+  // a one-column context's name is the kernel its last year ran on (the
+  // launch record of the shape; until a year runs, h9g_create's)
+  if (kind == K_PAIR1 && ctx->kind == K_PAIR1) ctx->kname = pair1_name(ctx, p1f);
   HIPCHK(hipEventRecord(ctx->ev1[e], ctx->sc));
   HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot], ctx->sc));
   if (two) HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot2], ctx->sc));
@@ -2995,6 +3096,17 @@ int h9g_sync(h9g_ctx *ctx) {
     fprintf(stderr, "h9g stamps (cycles/wave/substep):");
     for (int k = 0; k < 8; k++) { fprintf(stderr, " p%d=%.0f", k, sum[k] / steps); tot += sum[k]; }
     fprintf(stderr, " total=%.0f\n", tot / steps);
+    if (ctx->stamp_p1f) {
+      // the two-wave shape, by the launch's own record: p1 above is the main
+      // wave's wait at barrier 2; the front waves' records follow the grid's
+      // main waves' (pair_body: one main wave per workgroup)
+      std::vector<unsigned> fs(8 * nw);
+      HIPCHK(hipMemcpy(fs.data(), ctx->d_stamps + 8 * ctx->stamp_blocks, sizeof(unsigned) * 8 * nw, hipMemcpyDeviceToHost));
+      double w = 0, f = 0;
+      for (size_t k = 0; k < nw; k++) { w += fs[8 * k]; f += fs[8 * k + 1]; }
+      fprintf(stderr, "h9g stamps, front waves (cycles/wave/substep): wait at barrier 1=%.0f front=%.0f\n", w / steps,
+              f / steps);
+    }
     // load balance: per-wave totals (the kernel lasts as long as its slowest wave)
     std::vector<double> wt(nw, 0.0);
     for (size_t w = 0; w < nw; w++)

@@ -84,6 +84,22 @@ static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_
 #ifndef H9G_P1_TASKS
 #define H9G_P1_TASKS 7
 #endif
+// The one-column kernel's second wave per column (front_year_pair): lists of at
+// most H9G_PAIR1_FRONT_MAX cells run two waves per column, the front of the
+// substep on a wave of its own beside the per-layer rounds.  0 builds the
+// single-wave kernel only.
+#ifndef H9G_P1_FRONT
+#define H9G_P1_FRONT 1
+#endif
+// hydrology_pair's part of the substep: all of it; the front alone (everything
+// up to the equilibrium profile but theta(2..L): fsat, the beta terms, rss, the
+// energy balance, em1, infiltration), returning its results in FrontRes; or
+// everything but the front, which takes those results from the store's
+// hand-over rows behind a workgroup barrier.
+enum : int { ROLE_ALL = 0, ROLE_FRONT = 1, ROLE_MAIN = 2 };
+struct FrontRes {
+  float qflx_surf, tran, evg, qflx_infl;
+};
 
 template <int K>
 struct FV {
@@ -178,7 +194,7 @@ H9K_HD float hi_d(double v) {
 // kRts, kDayRecip say which reciprocal fields it holds (LDS budget).
 template <int L>
 struct FlatStore {                     // host: one flat array per cell
-  static constexpr bool kRecip = true, kRts = true, kDayRecip = true, kRtsHK = true, kSpare = false;
+  static constexpr bool kRecip = true, kRts = true, kDayRecip = true, kRtsHK = true, kSpare = false, kFront = false;
   static constexpr int N = PF_N * L + PS_N;
   float *b;
   const float *zt;                     // zi(0..L+1), then zi(0..L+1)/1000
@@ -306,9 +322,13 @@ constexpr int pair_resident() { return 3; }   // waves per SIMD (h9g.hip pair_wa
 // default, 168 VGPRs, <= 53 KB LDS per workgroup) or 2 (round 4, L = 10:
 // 256 VGPRs and 80 KB, so no spills and every reciprocal field; h9g.hip
 // h9g_pair2_kernel).
-template <int L, int S, int R = pair_resident<L>()>
+// F = 1: the one-column kernel's two-wave shape (front_year_pair); its block
+// ends with the hand-over rows HO_*.
+template <int L, int S, int R = pair_resident<L>(), int F = 0>
 struct PairStore {
   static constexpr int NT = L / 2;
+  static constexpr bool kFront = F != 0;
+  static_assert(!kFront || S == 2, "the front wave serves a one-column wave");
   // LDS fields by layer count (3 workgroups per CU: at most 75 rows).  L = 8:
   // every reciprocal (75 rows).  L = 10 (5 rows per per-layer field): 1/(-psi)
   // (~15 divisions per substep) instead of the day constants' reciprocals (~5;
@@ -326,7 +346,17 @@ struct PairStore {
   // NT more rows, float TH0 + i - 1 of the block, for its task lanes:
   // hydrology_pair)
   static constexpr int TH0 = (NPF * NT + (NPS + 1) / 2) * S;
-  static constexpr int ROWS = NPF * NT + (NPS + 1) / 2 + (S == 2 ? NT : 0);
+  // Hand-over words of the two-wave shape, floats of the block after theta:
+  // main -> front (written before barrier 1): smp(1..L), h2osoi_liq(1), zwt, go
+  // (0: evaluate this substep's front, else leave); front -> main (written
+  // before barrier 2): the FrontRes fields.  tests/test_pair1_front_map.py
+  // restates the map.
+  enum : int {
+    HO_SMP = TH0 + L, HO_H2O1 = HO_SMP + L, HO_ZWT, HO_GO, HO_PAD,
+    HO_SURF, HO_TRAN, HO_EVG, HO_INFL, HO_END
+  };
+  static_assert((HO_END - TH0 - L) % 2 == 0, "whole rows");
+  static constexpr int ROWS = NPF * NT + (NPS + 1) / 2 + (S == 2 ? NT : 0) + (kFront ? (HO_END - HO_SMP) / 2 : 0);
   static constexpr int GBLOCK = 65536;                      // bytes per workgroup (>= any LDS address)
   lds_float *self, *even;
   const lds_float *zt;                 // zi(0..L+1), then zi(0..L+1)/1000 (per block)
@@ -360,6 +390,17 @@ struct PairStore {
   __device__ __forceinline__ void launder() {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(self), "+v"(even), "+v"(zt)::"memory");
+#endif
+  }
+  // hand-over word k (HO_*), and the barrier of the column's two waves: what
+  // either wave stored to the block before it is read by the other after it
+  __device__ __forceinline__ float ho(int k) const { return wb[k]; }
+  __device__ __forceinline__ void set_ho(int k, float v) const { wb[k] = v; }
+  __device__ __forceinline__ void wg_sync() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #endif
   }
   __device__ __forceinline__ float day(int f) const { return sc(PS_DAY + f); }
@@ -414,7 +455,7 @@ struct PairStore {
 // (1054 waves = 5 blocks/CU), day snapshot in LDS.
 template <int L>
 struct SoloStore {
-  static constexpr bool kRecip = false, kRts = false, kDayRecip = false, kRtsHK = false, kSpare = false;
+  static constexpr bool kRecip = false, kRts = false, kDayRecip = false, kRtsHK = false, kSpare = false, kFront = false;
   static constexpr int NPF = PF_RPSI0 + 2;           // TS..ROOTR, SVH2O, SVSMP
   static constexpr int NPS = PS_LAI + 5;             // FMAX..DAY, SV*
   static constexpr int ROWS = NPF * L + NPS;
@@ -744,9 +785,12 @@ constexpr bool pair1_tasks() {
 // Under
 // Split2 the per-layer phases are split over the pair (file comment).
 // The end-of-step theta(1..L) of :1233 is left to the caller (end_theta).
-template <int L, class G, class M, class SP, class CS, class PR = NoProf>
+// ROLE (ROLE_*): the one-column kernel's two waves per column evaluate the
+// front (ROLE_FRONT, results into *fr) and the rest (ROLE_MAIN) of a substep
+// side by side; every other caller runs all of it.
+template <int L, class G, class M, class SP, class CS, class PR = NoProf, int ROLE = ROLE_ALL>
 H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf_sum, float &errval,
-                          M &m, PR &pr) {
+                          M &m, PR &pr, FrontRes *fr = nullptr) {
   constexpr int NT = L / 2;
   // At L = 10 the lane parity is made opaque here, so that values that
   // depend only on it -- a lane's geometry-table offsets of its own layers,
@@ -774,7 +818,13 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
 #define OWN(p) sp.own(cs, p, t, h)
 
   // :141-151
-  float w0 = DC(D_FORC) * dt + s.wa;
+  float w0 = zero;
+  if constexpr (ROLE == ROLE_FRONT) {
+    // the front reads theta(1) alone: the same quotient with the same redo
+    theta[1] = m.div_d(h2o[1], g.thk(1), g.rthk(1));
+    m.div_fix(theta[1], h2o[1], g.thk(1));
+  } else {
+  w0 = DC(D_FORC) * dt + s.wa;
   bool bad = false;                      // deferred checks (MathFast::div_d)
 #pragma unroll
   for (int i = 1; i <= L; i++) {
@@ -787,13 +837,16 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
 #pragma unroll
     for (int i = 1; i <= L; i++) m.div_fix(theta[i], h2o[i], g.thk(i));
   }
+  }
   // :161-212
-  const float qflx_top_soil = DC(D_FORC);
   const float hkdepth = one / 2.5f;
   const float fff = 1.0f / hkdepth;
-  const float fsat = cs.sc(PS_FMAX) * m.expf(-0.5f * fff * s.zwt);
-  float qflx_surf = fsat * qflx_top_soil;
   const float frac_h2osfc = zero;
+  float qflx_surf = zero, tran = zero, evg = zero, qflx_infl = zero;
+  if constexpr (ROLE != ROLE_MAIN) {       // the front (ROLE_MAIN: from the front wave, below)
+  const float qflx_top_soil = DC(D_FORC);
+  const float fsat = cs.sc(PS_FMAX) * m.expf(-0.5f * fff * s.zwt);
+  qflx_surf = fsat * qflx_top_soil;
   // :269-276 (previous-step smp)
   float beta = zero;
   {
@@ -833,7 +886,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     rss = (10.0f + DC(D_LIT1000) * (1.0f - divr<CS::kRts>(m, theta[1], TS(1), [&]() { return lay_d(cs, PF_RTS0, 1); })));
   const float desatdT = DC(D_DESAT), gamma = DC(D_GAMMA);
   const float Ra = DC(D_DG) * DC(D_RAA);
-  float rsc, tran, evg;
+  float rsc;
   bool eb_fast = false;
   if constexpr (H9G_EB_FAST && !M::kExact && CS::kDayRecip) {
     // The energy balance's chain of quotients (:283-389) branch-free: the
@@ -956,14 +1009,19 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   qflx_in_soil = qflx_in_soil - (one - frac_h2osfc) * qflx_evap;
   const float qinmax = (one - fsat) * cs.sc(PS_MH3);
   const float qflx_infl_excess = MAXF(zero, qflx_in_soil - (one - frac_h2osfc) * qinmax);
-  const float qflx_infl = qflx_in_soil - qflx_infl_excess;
+  qflx_infl = qflx_in_soil - qflx_infl_excess;
   qflx_surf = qflx_surf + qflx_infl_excess;
+  }  // the front
+  if constexpr (ROLE == ROLE_FRONT) {
+    *fr = FrontRes{qflx_surf, tran, evg, qflx_infl};
+    return 0;
+  }
   // :492-508
   float zwtmm = 1000.0f * s.zwt;
   const int jwt = jwt_of<L>(s.zwt, zim);
   const bool aq = (jwt == L);
   cs.launder();
-  pr.mark(1);
+  if constexpr (ROLE != ROLE_MAIN) pr.mark(1);
 
   // :517-567 equilibrium profile and :598-639 conductivity and matric
   // potential, own layers (independent phases)
@@ -1629,6 +1687,18 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   const float smp1 = eS.v[0], dsmpdw1 = eS.v[1];
   cs.launder();
   pr.mark(3);
+  if constexpr (ROLE == ROLE_MAIN) {
+    // barrier 2 (front_year_pair): the front wave's results of this substep,
+    // first read by the rows below.  Lanes 0 and 1 are here on every path (the
+    // helper lanes have returned); every STOP of this function lies below.
+    // Stamps: p1 is the wait here, the front wave's time that was not covered.
+    cs.wg_sync();
+    qflx_surf = cs.ho(CS::HO_SURF);
+    tran = cs.ho(CS::HO_TRAN);
+    evg = cs.ho(CS::HO_EVG);
+    qflx_infl = cs.ho(CS::HO_INFL);
+    pr.mark(1);
+  }
   // :645-650 aquifer node geometry
   const float zcA = 0.5f * (zwtmm + g.zc(L));
   const float dzA = (jwt < L) ? g.dz(L) : zwtmm - g.zc(L);
@@ -2195,7 +2265,9 @@ H9K_HD int substep_pair(const G &g, CS cs, const SP &sp, St<L> &s, float &rnf_su
 #elif defined(H9G_FORCE_RERUN_ANY)
   const bool in_column = true;                // test builds: also below the column (-> H9G_ERR_NOSNAP)
 #endif
-  int code = hydrology_pair<L, G, MathFast, SP, CS, PR>(g, cs, sp, s, rnf_sum, errval, mf, pr);
+  // (the two-wave shape's main wave: without the front, which its front wave evaluates)
+  int code = hydrology_pair<L, G, MathFast, SP, CS, PR, CS::kFront ? ROLE_MAIN : ROLE_ALL>(g, cs, sp, s, rnf_sum,
+                                                                                            errval, mf, pr);
 #if defined(H9G_FORCE_RERUN)
   // test builds: also re-run every H9G_FORCE_RERUN-th substep of a day that
   // could (the exact replay from the day snapshot must reproduce the fast
@@ -2281,6 +2353,97 @@ struct Months {
   }
 };
 
+// The one-column kernel's two waves per column (PairStore kFront; h9g.hip
+// h9g_pair1f_kernel: a workgroup is one column's main wave and front wave).
+//
+// A lone wave issues in order, so the front of the substep (hydrology_pair up
+// to the equilibrium profile: about a fifth of the substep, on lanes 0 and 1)
+// costs its own length whatever the rest of the SIMDs do.  It reads only the
+// previous substep's smp, h2osoi_liq(1), zwt, the day constants and the parked
+// plant state; the per-layer rounds A, B and C read none of its results.  So a
+// second wave evaluates it while the main wave runs theta and the rounds.
+//
+// Protocol: two workgroup barriers per substep, one buffer, no spinning.
+//   main wave (cell_year_pair)            front wave (front_year_pair)
+//     front_post: smp, h2o(1), zwt,
+//       go = 0 -> hand-over rows
+//     barrier 1 ------------------------- barrier 1
+//     theta, rounds A, B, C                 go != 0: leave
+//                                           the front from the rows posted
+//                                           FrontRes -> hand-over rows
+//     barrier 2 ------------------------- barrier 2
+//     FrontRes -> registers, p4..p7         (waits at the next barrier 1)
+//   at every exit of the year loop:
+//     front_done: go = 1, barrier 1 ----- barrier 1, go != 0: leave
+// The day constants, the parked plant state and rootr are the block's own
+// fields: the main wave writes them (day_consts, GROW) only between a
+// barrier 2 and the next barrier 1, when the front wave reads nothing.
+// One buffer is enough: the main wave rewrites the posted state after
+// barrier 2, when the front wave has read it, and the front wave rewrites
+// FrontRes after the next barrier 1, which the main wave reaches only after
+// its reads of them have completed (wg_sync waits for the wave's LDS traffic).
+//
+// Why no wave waits at a barrier its partner does not reach:
+//  - The main wave's sequence is (barrier 1, barrier 2) per substep, then one
+//    barrier 1 with go = 1; the front wave's is barrier 1, then (barrier 2,
+//    barrier 1) for as long as go = 0.  The front wave has no trip counts of
+//    its own: it follows go, so the two sequences match whatever ends the year.
+//  - Barrier 2 lies on the one path of hydrology_pair<ROLE_MAIN> that lanes 0
+//    and 1 take in every substep: no return of the function precedes it except
+//    the helper lanes' (lanes of the same wave, which stays).  Every STOP code
+//    of the function, H9G_ERR_NOSNAP_K and a STOP of the exact re-run (which
+//    evaluates its own front, ROLE_ALL, and holds no barrier) arise after it and
+//    leave through cell_year_pair's `code`.
+//  - cell_year_pair makes `code` wave-uniform (lane 0's) before it tests it, so
+//    the helper lanes leave the year loop with lanes 0 and 1 instead of running
+//    the year on alone, barriers included, as they harmlessly do in the
+//    single-wave kernel.  Both its exits -- a code, the year's end -- pass
+//    front_done once.
+//  - pair_body's early returns (slot past the list, non-land cell, stopped
+//    cell) are decided by both waves from the same global values before the
+//    first barrier 1; then neither wave reaches any.
+template <int L, class SP, class CS>
+H9K_HD void front_post(const SP &sp, const CS &cs, const St<L> &s) {
+#pragma unroll
+  for (int t = 0; t < L / 2; t++) cs.set_ho(CS::HO_SMP + 2 * t + sp.h, sel(sp.h, s.smp[2 * t + 1], s.smp[2 * t + 2]));
+  cs.set_ho(CS::HO_H2O1, s.h2o[1]);
+  cs.set_ho(CS::HO_ZWT, s.zwt);
+  cs.set_ho(CS::HO_GO, zero);
+}
+template <class CS>
+H9K_HD void front_done(const CS &cs) {
+  cs.set_ho(CS::HO_GO, one);
+  cs.wg_sync();
+}
+// The front wave's year: lanes 0 and 1 as the canopy and soil halves, as in the
+// main wave; no state, no stores but FrontRes.  pr: p0 its wait at barrier 1,
+// p1 the front.
+template <int L, class G, class SP, class CS, class PR = NoProf>
+H9K_HD void front_year_pair(const G &g, CS cs, const SP &sp, const h9m::Tabs &T, PR &&pr = PR()) {
+  if (sp.spare) return;
+  St<L> s{};
+  float rnf_sum = zero, errval = zero;
+  for (;;) {
+    cs.wg_sync();                                      // barrier 1
+    cs.launder();
+    if (lane0_get(cs.ho(CS::HO_GO)) != zero) break;
+    pr.mark(0);
+#pragma unroll
+    for (int i = 1; i <= L; i++) s.smp[i] = cs.ho(CS::HO_SMP + i - 1);
+    s.h2o[1] = cs.ho(CS::HO_H2O1);
+    s.zwt = cs.ho(CS::HO_ZWT);
+    MathFast mf{T, false};
+    FrontRes fr;
+    hydrology_pair<L, G, MathFast, SP, CS, PR, ROLE_FRONT>(g, cs, sp, s, rnf_sum, errval, mf, pr, &fr);
+    pr.mark(1);
+    cs.set_ho(CS::HO_SURF, fr.qflx_surf);
+    cs.set_ho(CS::HO_TRAN, fr.tran);
+    cs.set_ho(CS::HO_EVG, fr.evg);
+    cs.set_ho(CS::HO_INFL, fr.qflx_infl);
+    cs.wg_sync();                                      // barrier 2
+  }
+}
+
 // One calendar year for one cell (HYBRID9.f90:150-290), as cell_year.
 // Park = keep the plant state in the store over the substeps (register
 // relief for the 168-VGPR pair kernel).  MO: NoMonths or Months.
@@ -2364,7 +2527,12 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
         save_day<L>(sp, cs, s, rnf_sum, ns);
         snapped = true;
       }
+      if constexpr (CS::kFront) {            // the substep's state to the front wave (front_year_pair)
+        if (act) front_post<L>(sp, cs, s);
+        cs.wg_sync();                        // barrier 1
+      }
       code = substep_pair<L, G, SP, CS>(g, cs, sp, s, rnf_sum, errval, T, pr, ns, snapped);
+      if constexpr (CS::kFront) code = lane0_geti(code);   // the helper lanes leave with the pair
       if (code) { eday = day; estep = ns; break; }
     }
     cs.launder();
@@ -2376,7 +2544,10 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
       s.plen = cs.sc(PS_PLEN);
       s.rdepth = cs.sc(PS_RDEPTH);
     }
-    if (code) return code;
+    if (code) {
+      if constexpr (CS::kFront) front_done(cs);
+      return code;
+    }
     if (!act) continue;
     opaque(A);
     if (grow_on) {
@@ -2407,6 +2578,7 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
       if (later(k)) A[k * as] = a[k];
     mo.template day_end<L>(day, nt, A, as, rnf_sum);
   }
+  if constexpr (CS::kFront) front_done(cs);   // the year's end: the front wave leaves
   // :263-290
   if (!act) return 0;
   opaque(A);
