@@ -16,9 +16,9 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "csrc" / "h9g.hip"
-SRC_MON = HERE / "csrc" / "h9g_mon.hip"     # the monthly kernels: h9g.hip once more, with H9G_MONTHLY_UNIT
+SRC_MON = HERE / "csrc" / "h9g_mon.hip"     # the monthly kernels: h9g_year.h's kernels with the Months policy
 SRC_IO = HERE / "csrc" / "h9g_io.cpp"       # host-only NetCDF I/O
-DEPS = [SRC, SRC_MON, SRC_IO, HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
+DEPS = [SRC, SRC_MON, SRC_IO, HERE / "csrc" / "h9g_year.h", HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
         HERE / "csrc" / "h9g_synth.h", HERE / "csrc" / "h9g_geo.h",
         HERE / "csrc" / "h9g_pair.h", HERE / "csrc" / "h9g_expr.h", HERE / "csrc" / "h9g_rows.h",
         HERE / "csrc" / "h9g_io.h",
@@ -71,10 +71,11 @@ def _run(cmd, verbose):
 
 
 def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
-    """Compiles the three translation units to objects (the year kernels and
-    the monthly kernels, ~4 minutes each and side by side, and the host-only
-    NetCDF I/O, seconds; each only when its own inputs changed, keyed by
-    their digest) and links libh9g.so."""
+    """Compiles the three translation units to objects (h9g.hip with the year
+    kernels and everything else on the device, and h9g_mon.hip with the
+    monthly kernels, ~4 minutes each and side by side: both include
+    h9g_year.h; and the host-only NetCDF I/O, seconds; each only when its own
+    inputs changed, keyed by their digest) and links libh9g.so."""
     if not force and up_to_date():
         return OUT
     OUT.parent.mkdir(parents=True, exist_ok=True)
@@ -83,9 +84,9 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
     import hashlib
     flags = [f"--offload-arch={ARCH}", *FLAGS, *extra]
     objs, jobs = [], []
-    dev = [d for d in DEPS if d not in (SRC_IO, SRC_MON)]
+    hdrs = [d for d in DEPS if d not in (SRC, SRC_IO, SRC_MON)]
     # h9g_build_id lives in the I/O unit: only it gets the digest flag
-    for src, deps, idf in ((SRC, dev, []), (SRC_MON, [SRC_MON, *dev], []),
+    for src, deps, idf in ((SRC, [SRC, *hdrs], []), (SRC_MON, [SRC_MON, *hdrs], []),
                            (SRC_IO, [SRC_IO, HERE / "csrc" / "h9g_io.h", DEPS[-1]], [id_flag(extra)])):
         flags_u = flags + idf
         hs = hashlib.sha256(" ".join(flags_u).encode())

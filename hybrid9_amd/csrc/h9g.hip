@@ -26,6 +26,9 @@
 //   * no MFMA: nothing here is GEMM-shaped.
 //   * h9g_diag_kernel: deterministic FP64 reduction of global diagnostics
 //     (the payload of the cross-GPU all-reduce).
+// The year kernels, the table of their launch shapes and their launch are
+// h9g_year.h, shared with the monthly kernels' unit (h9g_mon.hip); this file
+// holds every other kernel and the host side.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -40,425 +43,20 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/h9g.h"
-#include "h9_math.h"
-#include "h9g_geo.h"
-#include "h9g_step.h"
-#include "h9g_pair.h"
-#include "h9g_rows.h"
+#include "h9g_year.h"
 #include "h9g_synth.h"
 #include "h9g_io.h"
 
-using namespace h9k;
 static_assert(H9G_ERR_NOSNAP_K == H9G_ERR_NOSNAP, "kernel and ABI error codes");
 static_assert(H9G_NDAILY == DAILY_ROWS, "the daily line of the ABI and of h9g_rows.h");
 
-__constant__ uint64_t c_exp2tab[32] = H9M_EXP2F_TAB_INIT;
-__constant__ double c_log2tab[32] = H9M_POWF_LOG2_TAB_INIT;
 static const uint64_t h_exp2tab[32] = H9M_EXP2F_TAB_INIT;
 static const double h_log2tab[32] = H9M_POWF_LOG2_TAB_INIT;
 
 #define H9G_BLOCK 256
-#define H9G_YBLOCK 64   // solo kernel: one wave per block (LDS cell stores)
-// pair kernel: 22 columns (44 lanes) per wave, 4 waves per workgroup; the
-// 0.5 deg grid is 767 workgroups = 3 waves on each of the 1,024 SIMDs
-#define H9G_PCPW 22
-#define H9G_PLANES (2 * H9G_PCPW)
-#define H9G_PWAVES 4
 #define NEVT 64
 static size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
-// ---------------------------------------------------------------------------
-// kernel arguments
-// ---------------------------------------------------------------------------
-struct KArgs {
-  int ncell;       // row stride of every per-cell array
-  int c0, cend;    // cells [c0, cend) of this launch
-  int nt;          // days in the year
-  int nisurf;
-  int grow_on;
-  size_t fvar;     // forcing variable stride (floats) = max_days * ncell
-  const float *__restrict__ par;   // parameter rows x ncell (h9g_rows.h)
-  float *__restrict__ st;          // state rows x ncell
-  const float *__restrict__ forc;  // 7 x max_days x ncell (slot base)
-  float *__restrict__ annual;      // annual rows x ncell
-  int *__restrict__ err;           // STOP record rows x ncell
-  int *__restrict__ err_flag;
-  unsigned *__restrict__ stamps;   // H9G_STAMPS builds: 8 phase cycle sums per wave
-  float *__restrict__ sv;          // pair kernel: day snapshot, PairStore::GBLOCK bytes per workgroup
-  const int *__restrict__ perm;    // lane slot -> cell (h9g_sort_kernel), or null: identity
-  int sorted_io;                   // 1: forc and annual are in slot order (h9g_perm_forcing_kernel; round 4)
-  int *__restrict__ hist;          // per cell: substeps of the year with the water table below the column
-  unsigned *__restrict__ pace;     // pair kernel, Pacer mode 2: H9G_PACE_ROWS x 16 progress words
-  unsigned epoch;                  // Pacer mode 2: launch tag
-  int prio_mode;                   // Pacer mode: 0 none, 1 rotate, 2 pace
-  // A second group of cells in the same launch (pair kernels; the cell-order
-  // mode's re-runs of one decade riding in the next decade's year launches,
-  // h9g_run_ordered).  Slots [c0, bend) are the first group; the waves from
-  // slot `split` (a multiple of the wave's column count, >= bend) to cend
-  // the second, with their own state and error rows, year length and no
-  // sort history.  split == cend: no second group.
-  int bend, split, nt2;
-  float *__restrict__ st2;
-  int *__restrict__ err2;
-  size_t iostride;                 // row stride of forc and annual when sorted_io (slots)
-  int raw;                         // 1: the annual rows are the running sums, undivided (the cell
-                                   // order's day-1 probe, h9g_probe_cmp_kernel)
-};
-
-// XCD-aware workgroup order.  MI355X deals the workgroups of a launch
-// round-robin to its 8 XCDs (workgroup b -> XCD b % 8), each with its own L2.
-// Workgroup b works on the cells of virtual workgroup xcd_vwg(b), which makes
-// each XCD's workgroups one contiguous range of cells: the forcing, annual
-// sums and state lines an XCD touches are its own (no line fetched by two
-// XCDs), and the per-year cell sort (h9g_sort_kernel) reorders cells only
-// within an XCD's range.
-#define H9G_NXCD 8
-__host__ __device__ __forceinline__ unsigned xcd_vwg(unsigned b, unsigned nb) {
-  const unsigned x = b % H9G_NXCD, q = nb / H9G_NXCD, r = nb % H9G_NXCD;
-  return x * q + (x < r ? x : r) + b / H9G_NXCD;
-}
-
-__device__ __forceinline__ void load_tabs(uint64_t *e2, double *l2) {
-  const int t = threadIdx.x;
-  if (t < 32) {
-    e2[t] = c_exp2tab[t];
-    l2[t] = c_log2tab[t];
-  }
-  __syncthreads();
-}
-
-// Pair kernel (h9g_pair.h): two lanes per soil column, the per-layer powers
-// split over the pair.  Same arguments, layouts and results as
-// h9g_year_kernel.
-// Waves per SIMD: 3 at L = 8 (168 VGPRs, 3 x 53 KB LDS per CU); 2 at L = 10,
-// where 168 VGPRs spill ~90 registers into the substep loop.
-template <int L>
-constexpr int pair_waves() { return pair_resident<L>(); }
-
-// C: columns (pairs) per wave: 22 (h9g_pair_kernel, h9g_pair2_kernel) or 11
-// (h9g_pair11_kernel: 42 helper lanes, 2 rounds per phase at L = 10).
-// MON: the monthly kernels (month-end snapshots of the running sums into
-// `mon`, addressed as a.annual: 12 * annual rows per cell).
-// FRONT: the one-column kernel's two-wave shape (h9g_pair.h front_year_pair):
-// a workgroup is one column, wave 0 its main wave and wave 1 its front wave,
-// both on the column's one LDS block.
-template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT = false>
-__device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr) {
-  typedef PairStore<L, 2 * C, R, FRONT ? 1 : 0> PS;
-  static_assert(!FRONT || C == 1, "the front wave serves a one-column wave");
-  constexpr int NW = FRONT ? 1 : H9G_PWAVES;               // column blocks per workgroup
-  __shared__ uint64_t s_e2[32];
-  __shared__ double s_l2[32];
-  __shared__ float s_cell[NW][PS::ROWS * 2 * C];           // [wave][row][lane]
-  __shared__ float s_zt[zt_size<L>()];
-  // the day snapshot addresses its global block by LDS byte offset
-  // (PairStore::svw): every static LDS address must lie inside GBLOCK
-  static_assert(sizeof(s_e2) + sizeof(s_l2) + sizeof(s_cell) + sizeof(s_zt) <= (size_t)PS::GBLOCK,
-                "pair kernel LDS footprint exceeds the day-snapshot block");
-  if (threadIdx.x == 0) fill_zt<L>(g, s_zt);
-  load_tabs(s_e2, s_l2);
-  const h9m::Tabs T = {s_e2, s_l2};
-  const int wave = FRONT ? 0 : threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // the front wave runs everything down to the year like the main wave: the
-  // same early returns from the same values, and the same values stored to the
-  // same words of the block (so it waits for nothing before its first barrier).
-  // The reverse must hold too: a front-wave store that lands late must not hit
-  // a word the main wave has rewritten meanwhile.  The prologue stores the
-  // parameter slots PF_TS..PF_PSI, PS_FMAX, PF_ROOTR and cell_inv_pair's fields
-  // (PF_NINVB..PF_RTS1, PS_MH3, PS_TSDZ1); before the first barrier 1 the main
-  // wave writes only park's plant state (PS_LAI..), day_consts' PS_DAY and
-  // PS_DR* and the HO_* words, and rootr not before the first day's end, many
-  // barriers later: the two sets are disjoint.  A field added to either side
-  // has to keep them so.
-  const bool front_wave = FRONT && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;
-  // lanes 0..43: 22 pairs; 44..63: spare lanes, which join the pairs only in
-  // the per-layer phases (Split2, hydrology_pair).  Spare lane 44 + j mirrors
-  // pair lane 12 + j (mod the wave's pair lanes): its LDS column and
-  // starting state, never stored to, so the substep code it runs masked-in
-  // stays ordinary; a pure function of the lane, so nothing about it is
-  // carried in registers.  Lanes 12..31 because an LDS read's lanes 32..63
-  // share one cycle (bank = dword mod 32): their columns' banks are the 20
-  // that pair lanes 32..43 leave free, so a mirrored read adds no conflict.
-  const bool spare = lane >= 2 * C;
-  if (spare && !PS::kSpare) return;
-  const int h = lane & 1;
-  const int slot0 = __builtin_amdgcn_readfirstlane(
-      a.c0 + (int)(xcd_vwg(blockIdx.x, gridDim.x) * NW + wave) * C);
-  // the wave's group (wave-uniform: split is a multiple of C)
-  const bool g2 = slot0 >= a.split;
-  const int lim = g2 ? a.cend : a.bend;
-  float *const st = g2 ? a.st2 : a.st;
-  int *const err = g2 ? a.err2 : a.err;
-  int *const hist = g2 ? nullptr : a.hist;
-  const int nt = g2 ? a.nt2 : a.nt;
-  const int ncol = min(C, lim - slot0);
-  if (ncol <= 0) return;             // an empty wave
-  const int pl = spare ? (lane - 2 * C + (C == H9G_PCPW ? 12 : 0)) % (2 * ncol) : lane;
-  const int slot = slot0 + (pl >> 1);
-  if (slot >= lim) return;           // both lanes of a pair leave together
-  const int c = a.perm ? a.perm[slot] : slot;
-  const int io = a.sorted_io ? slot : c;   // forcing and annual sums: slot order when sorted
-  const int n = a.ncell;
-  const size_t ios = a.sorted_io ? a.iostride : (size_t)n;
-
-  int prow, pslot;
-  pace_key(prow, pslot);
-  PS cs{(lds_float *)&s_cell[wave][pl], (lds_float *)&s_cell[wave][pl & ~1], (const lds_float *)s_zt,
-        a.sv + (size_t)blockIdx.x * (PS::GBLOCK / sizeof(float)),
-        Pacer{a.pace + (size_t)prow * 16, a.epoch & 0xfffffu, pslot, a.prio_mode,
-              (int)((blockIdx.x * (unsigned)PS::RESIDENT) / gridDim.x)},
-        (lds_float *)&s_cell[wave][0]};
-  const Split2 sp{h, lane, spare};
-  St<L> s;
-  if (!spare) {
-#pragma unroll
-    for (int p = PF_TS; p <= PF_PSI; p++)
-#pragma unroll
-      for (int t = 0; t < L / 2; t++) cs.set_slot(p, t, a.par[(size_t)par_row(L, p, 2 * t + h) * n + c]);
-    cs.set_sc(PS_FMAX, a.par[(size_t)Rows<L>::FMAX * n + c]);
-#pragma unroll
-    for (int t = 0; t < L / 2; t++) cs.set_slot(PF_ROOTR, t, st[(size_t)rootr_row(L, 2 * t + h) * n + c]);
-  }
-#pragma unroll
-  for (int i = 1; i <= L; i++) {
-    s.h2o[i] = st[(size_t)(Rows<L>::H2O + i - 1) * n + c];
-    s.smp[i] = st[(size_t)(Rows<L>::SMP + i - 1) * n + c];
-  }
-  H9K_LOAD_SCALARS(L, s, st, n, c)
-  cs.launder();
-
-  if (!spare) {
-    H9K_TS_SUM(L, cs, ts_sum)
-    if (!(ts_sum > SOIL_TRUNC) || err[c] != 0) {
-      if (h == 0 && !front_wave) nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
-      if constexpr (MON)
-        if (h == 0 && !front_wave) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
-      return;
-    }
-    cell_inv_pair<L, G>(g, cs);
-  }
-  if (__builtin_amdgcn_ballot_w64(!spare) == 0) return;   // every pair masked out: the spare lanes leave too
-  if constexpr (FRONT) {
-    if (front_wave) {
-#if defined(H9G_STAMPS)
-      StampProf fp{stamp_clock(), {0, 0, 0, 0, 0, 0, 0, 0}};
-      front_year_pair<L, G>(g, cs, sp, T, fp);
-      if (lane == 0 && a.stamps)            // the front waves' records follow the main waves'
-        for (int k = 0; k < 8; k++) a.stamps[(gridDim.x + blockIdx.x) * 8 + k] = fp.acc[k];
-#else
-      front_year_pair<L, G>(g, cs, sp, T);
-#endif
-      return;
-    }
-  }
-  int eday = 0, estep = 0;
-  float errval = 0.0f;
-#if defined(H9G_STAMPS)
-  StampProf pr{stamp_clock(), {0, 0, 0, 0, 0, 0, 0, 0}};
-  const int code = cell_year_pair<L, G, Split2, PS, true>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt,
-                                                         a.nisurf, a.grow_on, (gbl_float *)(a.annual + io), ios, eday,
-                                                         estep, errval, T, a.raw, pr);
-  if (lane == 0 && a.stamps)
-    for (int k = 0; k < 8; k++) a.stamps[(blockIdx.x * NW + wave) * 8 + k] = pr.acc[k];
-#else
-  int code;
-  if constexpr (MON)
-    code = cell_year_pair<L, G, Split2, PS, true, NoProf, Months>(
-        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf, a.grow_on,
-        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, NoProf(), Months{(gbl_float *)(mon + io), ios});
-  else
-    code = cell_year_pair<L, G>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf,
-                                a.grow_on, (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw);
-#endif
-  if (spare || h != 0) return;       // the even lane writes the cell back
-  int cw = c, iow = io;
-  opaque(cw);
-  opaque(iow);
-  cs.launder();
-  if (hist) hist[cw] = s.naq;
-  H9K_STORE_CELL(L, s, cs, st, n, cw, a.grow_on, SC_N)
-  if (code) {
-    stop_write(err, n, cw, code, eday, estep, errval, a.err_flag);
-    nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);
-    if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);
-  }
-}
-
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES)
-    __attribute__((amdgpu_waves_per_eu(pair_waves<L>(), pair_waves<L>())))
-h9g_pair_kernel(const KArgs a, const G g) {
-  pair_body<L, G, pair_waves<L>()>(a, g);
-}
-
-// The pair kernel built for 2 waves per SIMD (round 4):
-// 256 VGPRs, so the L = 10 substep does not spill (the 3-wave build spills
-// 108 VGPRs and 118 SGPRs into a 296-B-per-lane scratch that reaches HBM),
-// and 80 KB of LDS per workgroup, so every reciprocal field fits.  It trades
-// a third of the resident waves for that; l10_kind picks it by shard size.
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
-h9g_pair2_kernel(const KArgs a, const G g) {
-  pair_body<L, G, 2>(a, g);
-}
-
-// The pair kernel with 11 columns per wave (round 5): the 42
-// lanes past the pairs help in the per-layer phases, which then take 2
-// rounds instead of 5 at L = 10 (hydrology_pair helpers), and the wave's LDS
-// block halves, so every reciprocal field fits at 3 waves per SIMD.  Twice
-// the waves of 22-column ones for the same cells.  Measured on the 8-GPU
-// config-5 shard (33,750 cells: 3,069 waves for 3,072 slots) it lost to
-// pair2, so l10_kind never picks it; H9G_KERNEL=pair11
-// selects it, and the GPU tests run it.
-#define H9G_PCPW11 11
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(3, 3)))
-h9g_pair11_kernel(const KArgs a, const G g) {
-  pair_body<L, G, 3, H9G_PCPW11>(a, g);
-}
-
-// One column per wave (round 5): the 62 lanes past the pair help in the
-// per-layer phases, which take one round each (hydrology_pair helpers), and
-// the wave may hold every register (one wave per SIMD: no spills).  For the
-// short lists of the cell-order re-runs (h9g_run_decade_ordered), whose
-// years run as lone waves: a lone wave's year is latency-bound, and this
-// cuts its per-layer rounds from 3 to 1 at L = 8 (from 5 to 1 at L = 10).
-// Round 7: its powers of the per-layer phases, the single-power round and the
-// aquifer node run as two task rounds, a power per lane (hydrology_pair kTask).
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(1, 1)))
-h9g_pair1_kernel(const KArgs a, const G g) {
-  pair_body<L, G, 1, 1>(a, g);
-}
-// Its two-wave shape (round 9): a workgroup is one column, whose second wave
-// evaluates the front of each substep beside the first wave's per-layer rounds
-// (h9g_pair.h front_year_pair).  Twice the waves per cell, one per SIMD still:
-// for lists of at most H9G_PAIR1_FRONT_MAX cells (pair1_front); longer lists
-// keep the single-wave kernel above.  Both run as kind K_PAIR1.
-#define H9G_PAIR1_FRONT_MAX 512
-#if H9G_P1_FRONT
-template <int L, class G>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
-h9g_pair1f_kernel(const KArgs a, const G g) {
-  pair_body<L, G, 1, 1, false, true>(a, g);
-}
-#endif
-
-
-// Solo kernel: one lane per soil column running the generic code of
-// h9g_pair.h with one lane doing every layer (SplitAll: two layers per
-// scheduling region, tridiagonal rows eliminated as assembled).
-// The body is a macro, expanded in place in the kernel and in its monthly
-// sibling (MON, `mon`: pair_body's): as an inlined function the same
-// statements compiled to other machine code for the kernel (blockDim.x loaded
-// from the dispatch packet; as with the row macros of h9g_rows.h).
-#define H9G_SOLO_BODY(MON, mon)                                                                                    \
-  typedef SoloStore<L> SS;                                                                                         \
-  __shared__ uint64_t s_e2[32];                                                                                    \
-  __shared__ double s_l2[32];                                                                                      \
-  __shared__ float s_cell[SS::ROWS * H9G_YBLOCK];                                                                  \
-  __shared__ float s_zt[zt_size<L>()];                                                                             \
-  if (threadIdx.x == 0) fill_zt<L>(g, s_zt);                                                                       \
-  load_tabs(s_e2, s_l2);                                                                                           \
-  const h9m::Tabs T = {s_e2, s_l2};                                                                                \
-  const int slot = a.c0 + (int)(xcd_vwg(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x);                        \
-  if (slot >= a.cend) return;                                                                                      \
-  const int c = a.perm ? a.perm[slot] : slot;                                                                      \
-  const int io = a.sorted_io ? slot : c;                                                                           \
-  const int n = a.ncell;                                                                                           \
-  const size_t ios = a.sorted_io ? a.iostride : (size_t)n;                                                         \
-  SS cs{(lds_float *)&s_cell[threadIdx.x], (const lds_float *)s_zt};                                               \
-  const SplitAll sp;                                                                                               \
-  St<L> s;                                                                                                         \
-  H9K_LOAD_LANE(L, cs, s, a.par, n, c, a.st, n, c)                                                                 \
-  H9K_LOAD_SCALARS(L, s, a.st, n, c)                                                                               \
-  cs.launder();                                                                                                    \
-  H9K_TS_SUM(L, cs, ts_sum)                                                                                        \
-  if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {                                                                   \
-    nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);                                                                  \
-    if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);                                      \
-    return;                                                                                                        \
-  }                                                                                                                \
-  cell_inv_pair<L, G>(g, cs);                                                                                      \
-  int eday = 0, estep = 0;                                                                                         \
-  float errval = 0.0f;                                                                                             \
-  int code;                                                                                                        \
-  if constexpr (MON)                                                                                               \
-    code = cell_year_pair<L, G, SplitAll, SS, false, NoProf, Months>(                                              \
-        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, a.nt, a.nisurf, a.grow_on,                    \
-        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, NoProf(),                                \
-        Months{(gbl_float *)(mon + io), ios});                                                                     \
-  else                                                                                                             \
-    code = cell_year_pair<L, G, SplitAll, SS, false>(g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar,  \
-                                                     a.nt, a.nisurf, a.grow_on, (gbl_float *)(a.annual + io), ios, \
-                                                     eday, estep, errval, T, a.raw);                               \
-  int cw = c, iow = io;                                                                                            \
-  opaque(cw);                                                                                                      \
-  opaque(iow);                                                                                                     \
-  cs.launder();                                                                                                    \
-  if (a.hist) a.hist[cw] = s.naq;                                                                                  \
-  H9K_STORE_CELL(L, s, cs, a.st, n, cw, a.grow_on, SC_N)                                                           \
-  if (code) {                                                                                                      \
-    stop_write(a.err, n, cw, code, eday, estep, errval, a.err_flag);                                               \
-    nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);                                                                 \
-    if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);                                     \
-  }
-
-template <int L, class G>
-__global__ void __launch_bounds__(H9G_YBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
-h9g_solo_kernel(const KArgs a, const G g) {
-  H9G_SOLO_BODY(false, ((float *)nullptr))
-}
-
-// The monthly kernels (h9g_set_monthly): each year kernel once more under a
-// name of its own, with the Months policy of cell_year_pair and the base of
-// the monthly rows as an argument after KArgs -- KArgs itself is unchanged, so
-// the kernels above keep their argument layout and their machine code.
-// Launched only by a context with monthly recording on, never by a probe.
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES)
-    __attribute__((amdgpu_waves_per_eu(pair_waves<L>(), pair_waves<L>())))
-h9g_pair_mon_kernel(const KArgs a, float *mon, const G g) {
-  pair_body<L, G, pair_waves<L>(), H9G_PCPW, true>(a, g, mon);
-}
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
-h9g_pair2_mon_kernel(const KArgs a, float *mon, const G g) {
-  pair_body<L, G, 2, H9G_PCPW, true>(a, g, mon);
-}
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(3, 3)))
-h9g_pair11_mon_kernel(const KArgs a, float *mon, const G g) {
-  pair_body<L, G, 3, H9G_PCPW11, true>(a, g, mon);
-}
-template <int L, class G>
-__global__ void __launch_bounds__(64 * H9G_PWAVES) __attribute__((amdgpu_waves_per_eu(1, 1)))
-h9g_pair1_mon_kernel(const KArgs a, float *mon, const G g) {
-  pair_body<L, G, 1, 1, true>(a, g, mon);
-}
-#if H9G_P1_FRONT
-template <int L, class G>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
-h9g_pair1f_mon_kernel(const KArgs a, float *mon, const G g) {
-  pair_body<L, G, 1, 1, true, true>(a, g, mon);
-}
-#endif
-template <int L, class G>
-__global__ void __launch_bounds__(H9G_YBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
-h9g_solo_mon_kernel(const KArgs a, float *mon, const G g) {
-  H9G_SOLO_BODY(true, mon)
-}
-
-// The monthly kernels are compiled in a translation unit of their own
-// (h9g_mon.hip: this file with H9G_MONTHLY_UNIT, which keeps the year
-// kernels' code above, the kernel kinds and the geometry dispatch below, and
-// h9g_mon_launch), beside this one, so the two build at the same time.
-int h9g_mon_launch(int kind, bool p1f, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream,
-                   const KArgs &a, float *mon);
-int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);
-
-#if !defined(H9G_MONTHLY_UNIT)
 // The year's forcing in the year kernel's slot order (round 4, VERDICT r03
 // #5): dst[v][d][s] = src[v][d][perm[s]].  With the cells re-ordered each
 // year (h9g_sort_kernel), a wave's daily forcing loads by cell id scattered
@@ -1126,56 +724,9 @@ __global__ void h9g_math_fast_kernel(int n, const float *x, const float *y, floa
   flag[i] = mf.redone ? 1 : 0;
 }
 
-#endif  // !H9G_MONTHLY_UNIT
-
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// Kernel kinds: what a context runs its years on (h9g_ctx::kind, H9G_KERNEL)
-// and what a launch ran on (the rows of h9g_launch_stats, which the Python
-// layer names: the numbers stay).
-enum Kind : int {
-  K_PAIR = 1,     // h9g_pair_kernel
-  K_SOLO = 2,     // h9g_solo_kernel
-  K_MIXED = 3,    // whole rounds of solo waves, then the pair kernel on the rest (l10_kind)
-  K_PAIR2 = 4,    // h9g_pair2_kernel (L = 10)
-  K_PAIR11 = 5,   // h9g_pair11_kernel
-  K_PAIR1 = 6,    // h9g_pair1_kernel
-  K_PROBE = 7,    // statistics only: the cell order's day-1 probes, whatever kernel ran them
-  K_NSTAT         // rows of h9g_ctx::kstat
-};
-struct KindInfo {
-  const char *env;      // H9G_KERNEL value
-  int wave_cols;        // columns per wave (of its pair part)
-  int resident;         // workgroups resident per CU = waves per SIMD (the Pacer's round, pace_mode)
-  bool pair;            // launches a pair kernel (day-snapshot blocks, pacing rows)
-  bool second_group;    // its launches can carry a second group of cells (g2_fits)
-  Kind pair_part;       // the kind its pair part, and a list launch of its context, runs as
-  int block_cells;      // cells per workgroup (of its pair part)
-};
-static constexpr KindInfo kind_info(int kind) {
-  switch (kind) {
-    // (the solo kernel does not pace: its `resident` only fills KArgs::prio_mode as the pair kernel's would)
-    case K_SOLO: return {"solo", H9G_YBLOCK, pair_resident<8>(), false, false, K_SOLO, H9G_YBLOCK};
-    case K_MIXED: return {"mixed", H9G_PCPW, pair_resident<8>(), true, false, K_PAIR, H9G_PCPW * H9G_PWAVES};
-    case K_PAIR2: return {"pair2", H9G_PCPW, 2, true, true, K_PAIR2, H9G_PCPW * H9G_PWAVES};
-    case K_PAIR11: return {"pair11", H9G_PCPW11, pair_resident<8>(), true, true, K_PAIR11, H9G_PCPW11 * H9G_PWAVES};
-    case K_PAIR1: return {"pair1", 1, 1, true, false, K_PAIR1, H9G_PWAVES};
-    default: return {"pair", H9G_PCPW, pair_resident<8>(), true, true, K_PAIR, H9G_PCPW * H9G_PWAVES};
-  }
-}
-
-// The one-column kernel runs a launch of at most H9G_PAIR1_FRONT_MAX cells in
-// its two-wave shape, a workgroup per cell (h9g_pair1f_kernel: still at most
-// one wave per SIMD).  Decided by the launch's cells alone.
-static bool pair1_front(size_t cells) { return H9G_P1_FRONT && cells <= H9G_PAIR1_FRONT_MAX; }
-// Cells per workgroup of a launch of `kind`; p1f: in the one-column kernel's
-// two-wave shape.  run_year_impl decides p1f once per launch, from the
-// launch's cells, and hands it to everything that depends on the shape: the
-// sort's and the forcing gather's traversal, the grid, launch_year's block
-// size and kernel, the monthly dispatch, the name of the kernel that ran.
-static int launch_block_cells(int kind, bool p1f) { return p1f ? 1 : kind_info(kind).block_cells; }
-
 struct h9g_ctx {
   h9g_config cfg;
   int device = 0;
@@ -1197,7 +748,7 @@ struct h9g_ctx {
   int last_year = 0;
   int params_set = 0, state_set = 0, ran = 0;
   h9g_error last_err{};
-  std::string kname, targs;       // the year kernel's name; its template arguments
+  std::string kname;              // the year kernel's name (year_kernel_name)
   unsigned *d_stamps = nullptr;   // H9G_STAMPS builds only
   std::vector<int64_t> h_gid;     // grid ids of the cells (h9g_set_cells), for NetCDF ingest
   std::vector<float *> h_pin;     // per-slot pinned staging of the NetCDF prefetch
@@ -1228,7 +779,7 @@ struct h9g_ctx {
   size_t n_solo = 0;   // K_MIXED: cells [0, n_solo) run on the solo kernel, the rest on the pair kernel
   size_t ios = 0;      // slots of the slot-ordered buffers (d_perm, d_forc_s, d_ann_s): twice the cells
   size_t stamp_words = 0;
-  bool stamp_p1f = false;         // the last stamped launch: run_year_impl's shape decision ...
+  Shape stamp_shape = S_PAIR;     // the last stamped launch: its shape ...
   size_t stamp_blocks = 0;        // ... and its grid (the front waves' records follow the grid's main waves')
   int ev_kind[NEVT] = {};         // kernel kind and cell-years of each timed launch
   int64_t ev_cells[NEVT] = {};
@@ -1258,11 +809,6 @@ struct h9g_ctx {
   bool mon_in_ret = false;        // ... in d_mon_ret (an ordered call) or d_mon (h9g_run_year)
 };
 
-// The one-column kernel's name by shape (p1f: the two-wave shape).
-static std::string pair1_name(const h9g_ctx *ctx, bool p1f) {
-  return std::string("h9g_pair1") + (p1f ? "f" : "") + "_kernel" + ctx->targs;
-}
-
 static void ord_free(h9g_ctx *ctx);
 
 #define HIPCHK(x)                                                              \
@@ -1282,131 +828,18 @@ static int days_in_year(int y) {   // INIT.f90:844-859
   return 366;
 }
 
-// Kernel variant for a context: compile-time geometry when zi is one of
-// the built-in layer sets and NISURF is 24 or 48, runtime geometry otherwise.
-enum GeoKind { GEO_R = 0, GEO_C24 = 24, GEO_C48 = 48 };
-
-static GeoKind geo_kind(const h9g_config &c) {
-  const float *zd = c.nlayers == 8 ? ZiDefault<8>::zi : ZiDefault<10>::zi;
-  for (int i = 0; i <= c.nlayers + 1; i++)
-    if (c.zi[i] != zd[i]) return GEO_R;
-  if (c.nisurf == 24) return GEO_C24;
-  if (c.nisurf == 48) return GEO_C48;
-  return GEO_R;
-}
-
-// Launch a templated kernel K<L, G> with the context's geometry variant.
-#if defined(H9G_ONLY_C2)
-// A/B measurement builds (tools/build_variant.py --c2): the driver's config-2
-// instantiation only (L = 8, driver.txt layers, NISURF = 48), ~1 minute
-// instead of ~4 to build; any other configuration is refused.
-#define H9G_DISPATCH(ctx, KERNEL, GRID, BLOCK, STREAM, ...)                          \
-  do {                                                                               \
-    if ((ctx)->L != 8 || geo_kind((ctx)->cfg) != GEO_C48) {                          \
-      fprintf(stderr, "h9g: H9G_ONLY_C2 build runs config 2 only\n");                \
-      return H9G_EINVAL;                                                             \
-    }                                                                                \
-    KERNEL<8, GeoC<8, 48>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<8, 48>());  \
-  } while (0)
-#else
-#define H9G_DISPATCH(ctx, KERNEL, GRID, BLOCK, STREAM, ...)                          \
-  do {                                                                               \
-    const GeoKind gk_ = geo_kind((ctx)->cfg);                                        \
-    if ((ctx)->L == 8) {                                                             \
-      if (gk_ == GEO_C48)                                                            \
-        KERNEL<8, GeoC<8, 48>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<8, 48>()); \
-      else if (gk_ == GEO_C24)                                                       \
-        KERNEL<8, GeoC<8, 24>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<8, 24>()); \
-      else                                                                           \
-        KERNEL<8, GeoR<8>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__,                  \
-                                                       make_geo_r<8>((ctx)->cfg.zi, (ctx)->cfg.nisurf)); \
-    } else {                                                                         \
-      if (gk_ == GEO_C48)                                                            \
-        KERNEL<10, GeoC<10, 48>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<10, 48>()); \
-      else if (gk_ == GEO_C24)                                                       \
-        KERNEL<10, GeoC<10, 24>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<10, 24>()); \
-      else                                                                           \
-        KERNEL<10, GeoR<10>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__,                \
-                                                         make_geo_r<10>((ctx)->cfg.zi, (ctx)->cfg.nisurf)); \
-    }                                                                                \
-  } while (0)
-#endif
-
-// Launch a kernel that exists at L = 10 only (h9g_pair2_kernel).
-#if defined(H9G_ONLY_C2)
-#define H9G_DISPATCH_L10(ctx, KERNEL, GRID, BLOCK, STREAM, ...) \
-  do {                                                          \
-    fprintf(stderr, "h9g: H9G_ONLY_C2 build runs config 2 only\n"); \
-    return H9G_EINVAL;                                          \
-  } while (0)
-#else
-#define H9G_DISPATCH_L10(ctx, KERNEL, GRID, BLOCK, STREAM, ...)                         \
-  do {                                                                              \
-    const GeoKind gk_ = geo_kind((ctx)->cfg);                                       \
-    if (gk_ == GEO_C48)                                                             \
-      KERNEL<10, GeoC<10, 48>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<10, 48>()); \
-    else if (gk_ == GEO_C24)                                                        \
-      KERNEL<10, GeoC<10, 24>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__, GeoC<10, 24>()); \
-    else                                                                            \
-      KERNEL<10, GeoR<10>><<<GRID, BLOCK, 0, STREAM>>>(__VA_ARGS__,                 \
-                                                       make_geo_r<10>((ctx)->cfg.zi, (ctx)->cfg.nisurf)); \
-  } while (0)
-#endif
-
-#if defined(H9G_ISA_ONLY)
-// tools/isa_pair.sh: device code of the config-2 pair kernel alone (ISA study)
-#if defined(H9G_ISA_L10)
-template __global__ void h9g_pair_kernel<10, GeoC<10, 24>>(const KArgs, const GeoC<10, 24>);
-template __global__ void h9g_pair2_kernel<10, GeoC<10, 24>>(const KArgs, const GeoC<10, 24>);
-template __global__ void h9g_pair11_kernel<10, GeoC<10, 24>>(const KArgs, const GeoC<10, 24>);
-#else
-template __global__ void h9g_pair1_kernel<8, GeoC<8, 48>>(const KArgs, const GeoC<8, 48>);
-template __global__ void h9g_pair_kernel<8, GeoC<8, 48>>(const KArgs, const GeoC<8, 48>);
-#endif
-#elif defined(H9G_MONTHLY_UNIT)
-// The cell order: the cells that start a decade stopped (err0) run none
-// of its years; all their monthly rows of the decade (`rows` of n) are NaN.
-__global__ void __launch_bounds__(256) h9g_stopped_mon_kernel(int n, int rows, const int *__restrict__ err0,
-                                                              float *__restrict__ mon) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n || err0[c] == 0) return;
-  for (int r = 0; r < rows; r++) mon[(size_t)r * n + c] = __builtin_nanf("");
-}
-
-int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream) {
-  h9g_stopped_mon_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(n, rows, err0, mon);
-  return 0;
-}
-
-// The monthly kernel of a launch of `kind` (not K_MIXED: launch_year cuts
-// that into its two parts) with the configuration's geometry variant.
-// p1f: the one-column kernel's two-wave shape (run_year_impl's decision).
-int h9g_mon_launch(int kind, bool p1f, const h9g_config *cfg, unsigned grid, unsigned block, hipStream_t stream,
-                   const KArgs &a, float *mon) {
-  const struct { int L; h9g_config cfg; } c{cfg->nlayers, *cfg};
-  switch (kind) {
-    case K_SOLO: H9G_DISPATCH(&c, h9g_solo_mon_kernel, grid, block, stream, a, mon); break;
-    case K_PAIR2:
-      if (c.L != 10) return H9G_EINVAL;
-      H9G_DISPATCH_L10(&c, h9g_pair2_mon_kernel, grid, block, stream, a, mon);
-      break;
-    case K_PAIR11: H9G_DISPATCH(&c, h9g_pair11_mon_kernel, grid, block, stream, a, mon); break;
-    case K_PAIR1:
-#if H9G_P1_FRONT
-      if (p1f) {
-        H9G_DISPATCH(&c, h9g_pair1f_mon_kernel, grid, block, stream, a, mon);
-        break;
-      }
-#endif
-      H9G_DISPATCH(&c, h9g_pair1_mon_kernel, grid, block, stream, a, mon);
-      break;
-    case K_PAIR: H9G_DISPATCH(&c, h9g_pair_mon_kernel, grid, block, stream, a, mon); break;
-    default: return H9G_EINVAL;
-  }
-  return 0;
-}
-#else
 static unsigned nblocks(size_t n) { return (unsigned)((n + H9G_BLOCK - 1) / H9G_BLOCK); }
+
+// What h9g_kernel_name reports for a year of `cells` cells on `kind`:
+// "h9g_pair_kernel<8,GeoC<8,48>>"; the mixed kind: its solo kernel + its pair
+// kernel.  (hybrid9_amd kind_id reads the prefix.)
+static std::string year_kernel_name(const h9g_ctx *ctx, int kind, size_t cells) {
+  const GeoKind gk = geo_kind(ctx->cfg);
+  const std::string L = std::to_string(ctx->L);
+  const std::string targs = "<" + L + "," + (gk == GEO_R ? "GeoR" : "GeoC<" + L + "," + std::to_string((int)gk) + ">") + ">";
+  auto name = [&](int k) { return shape_info(year_shape(k, cells)).name + targs; };
+  return kind == K_MIXED ? name(K_SOLO) + "+" + name(K_PAIR) : name(kind);
+}
 
 extern "C" {
 
@@ -1489,8 +922,7 @@ void h9g_destroy(h9g_ctx *ctx) {
 static Kind l10_kind(size_t n, int ncu, size_t *n_solo) {
   const size_t solo_round = (size_t)4 * ncu * H9G_YBLOCK;
   *n_solo = (n / solo_round) * solo_round;
-  const size_t blocks = (n + (size_t)H9G_PCPW * H9G_PWAVES - 1) / ((size_t)H9G_PCPW * H9G_PWAVES);
-  return blocks <= (size_t)kind_info(K_PAIR2).resident * ncu ? K_PAIR2 : K_PAIR;
+  return shape_blocks(S_PAIR2, n) <= (size_t)shape_info(S_PAIR2).waves * ncu ? K_PAIR2 : K_PAIR;
 }
 
 // Device bytes a context of this configuration allocates: h9g_create's
@@ -1519,7 +951,7 @@ size_t h9g_config_bytes(const h9g_config *cfg) {
   // the largest launch's day-snapshot blocks: the 11-column kernel's over
   // every cell, or the one-column kernel's over H9G_PAIR1_MAX listed cells
   // (a workgroup per cell up to H9G_PAIR1_FRONT_MAX)
-  const size_t blocks = std::max((ios + (size_t)H9G_PCPW11 * H9G_PWAVES - 1) / ((size_t)H9G_PCPW11 * H9G_PWAVES),
+  const size_t blocks = std::max(shape_blocks(S_PAIR11, ios),
                                  std::max((size_t)1024 / H9G_PWAVES, (size_t)H9G_PAIR1_FRONT_MAX));
   // + the slot-ordered copies of a forcing slot and of the annual sums
   // (h9g_run_year, allocated on first use), the ordered mode's decade
@@ -1673,17 +1105,7 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
     ctx->kind = K_PAIR;
   else
     ctx->kind = l10_kind(n, ncu, &ctx->n_solo);
-  // "h9g_pair_kernel<8,GeoC<8,48>>"; the mixed kind: its solo kernel + its pair kernel.  Every kernel is
-  // named h9g_<its H9G_KERNEL value>_kernel: KindInfo::env spells both (hybrid9_amd kind_id reads the prefix)
-  const GeoKind gk = geo_kind(*cfg);
-  const std::string targs = "<" + std::to_string(L) + "," +
-                            (gk == GEO_R ? "GeoR" : "GeoC<" + std::to_string(L) + "," + std::to_string((int)gk) + ">") + ">";
-  ctx->targs = targs;
-  // (a one-column context of few cells runs every year in the two-wave shape)
-  auto kernel_name = [&](int k) {
-    return k == K_PAIR1 ? pair1_name(ctx, pair1_front(ctx->n)) : "h9g_" + std::string(kind_info(k).env) + "_kernel" + targs;
-  };
-  ctx->kname = ctx->kind == K_MIXED ? kernel_name(K_SOLO) + "+" + kernel_name(K_PAIR) : kernel_name(ctx->kind);
+  ctx->kname = year_kernel_name(ctx, ctx->kind, ctx->n);
   return ctx;
 }
 
@@ -1728,7 +1150,11 @@ int h9g_init_state(h9g_ctx *ctx) {
   if (!ctx->params_set) return H9G_ESTATE;
   HIPCHK(hipSetDevice(ctx->device));
   const int n = (int)ctx->n;
-  H9G_DISPATCH(ctx, h9g_init_kernel, nblocks(n), H9G_BLOCK, ctx->sc, n, ctx->d_par, ctx->d_st);
+  if (int rc = geo_dispatch(ctx->cfg, [&](auto L, auto g) {
+        h9g_init_kernel<L, decltype(g)><<<nblocks(n), H9G_BLOCK, 0, ctx->sc>>>(n, ctx->d_par, ctx->d_st, g);
+        return 0;
+      }))
+    return rc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int) * STOP_ROWS * ctx->n, ctx->sc));
   HIPCHK(hipMemsetAsync(ctx->d_errflag, 0, sizeof(int), ctx->sc));
@@ -1822,23 +1248,25 @@ static int join_prefetch(h9g_ctx *ctx, int slot) {
 // Pacer mode of a pair launch of `blocks` workgroups (h9g_pair.h Pacer): pace
 // when all of them are resident at once (one round), else rotate -- a wave of
 // a later round starts hundreds of days behind the waves it shares a SIMD with.
-static int pace_mode(const h9g_ctx *ctx, int kind, size_t blocks) {
+// (The solo kernel does not pace: its launches carry the mode the pair kernel's would.)
+static int pace_mode(const h9g_ctx *ctx, Shape shape, size_t blocks) {
   if (ctx->prio_mode >= 0) return ctx->prio_mode;
-  return blocks <= (size_t)ctx->ncu * kind_info(kind).resident ? 2 : 1;
+  return blocks <= (size_t)ctx->ncu * shape_info(shape_info(shape).pair ? shape : S_PAIR).waves ? 2 : 1;
 }
 
 // Whether a year launch of `base` cells on the context's kernel can carry k
-// more cells in a second group for free: a pair kernel kind, and the extra
-// waves fit the launch's last round of resident workgroups.
+// more cells in a second group for free: a pair kernel kind (not the mixed
+// one, whose year is two launches), and the extra waves fit the launch's last
+// round of resident workgroups.
 static bool g2_fits(const h9g_ctx *ctx, size_t base, size_t k) {
-  const KindInfo ki = kind_info(ctx->kind);
-  if (k == 0 || !ctx->sort || !ki.second_group) return false;
+  const ShapeInfo si = shape_info(year_shape(ctx->kind, base));
+  if (k == 0 || !ctx->sort || ctx->kind == K_MIXED || !si.second_group) return false;
 #if defined(H9G_DUMP_AQ)
   return false;
 #endif
-  const size_t C = (size_t)ki.wave_cols, per = (size_t)ki.block_cells;
+  const size_t C = (size_t)si.wave_cols, per = (size_t)si.block_cells();
   if (round_up(base, C) + k > ctx->ios) return false;
-  const size_t slots = (size_t)ctx->ncu * ki.resident;
+  const size_t slots = (size_t)ctx->ncu * si.waves;
   const size_t b1 = (base + per - 1) / per, b2 = (round_up(base, C) + k + per - 1) / per;
   return (b2 + slots - 1) / slots == (b1 + slots - 1) / slots;
 }
@@ -1901,72 +1329,58 @@ static Kind list_kind(const h9g_ctx *ctx, int m) {
   if (ctx->kind == K_SOLO) return K_SOLO;
   if (m <= H9G_PAIR1_MAX && !getenv("H9G_NO_PAIR1")) return K_PAIR1;
   if (ctx->L == 8 && ctx->kind == K_PAIR && m <= H9G_PAIR11_LIST && !getenv("H9G_NO_PAIR11")) return K_PAIR11;
-  return kind_info(ctx->kind).pair_part;
+  return shape_info(kind_info(ctx->kind).shape).kind;
 }
 
 // The launch ranges of an every-cell year on the context's kernel: cells
-// [c0, cend) in workgroups of cpb cells.  One range, or for the mixed kind
+// [c0, cend) in workgroups of `shape`.  One range, or for the mixed kind
 // [0, n_solo) in solo blocks and [n_solo, n) in pair blocks.
-struct LaunchRange { int c0, cend, cpb; Kind kind; };
+struct LaunchRange {
+  int c0, cend;
+  Shape shape;
+  int cpb() const { return shape_info(shape).block_cells(); }
+};
 static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
-  // (an every-cell launch: run_year_impl's decision for the context's n cells)
   const int n = (int)ctx->n, ns = (int)ctx->n_solo;
-  const int cpb = launch_block_cells(ctx->kind, ctx->kind == K_PAIR1 && pair1_front(ctx->n));
   int k = 0;
   if (ctx->kind != K_MIXED) {
-    r[k++] = {0, n, cpb, ctx->kind};
+    r[k++] = {0, n, year_shape(ctx->kind, ctx->n)};
   } else {
-    if (ns > 0) r[k++] = {0, ns, H9G_YBLOCK, K_SOLO};
-    if (ns < n) r[k++] = {ns, n, cpb, K_PAIR};
+    if (ns > 0) r[k++] = {0, ns, S_SOLO};
+    if (ns < n) r[k++] = {ns, n, S_PAIR};
   }
   return k;
 }
 
-// The year kernel of a launch of `kind` over a's slots: `blocks` workgroups
-// of its pair part; the mixed kind over year_ranges' two.
-// mon: the base of the launch's monthly rows; then the kind's monthly kernel.
-// p1f (K_PAIR1 only): the two-wave shape, workgroups of two waves and `blocks`
-// of one cell each.
-static int launch_year(h9g_ctx *ctx, int kind, KArgs a, size_t blocks, float *mon, bool p1f) {
-  const unsigned pb = (unsigned)blocks, pt = p1f ? 128 : 64 * H9G_PWAVES;
-  if (mon && kind != K_MIXED) {
-    const bool solo = kind == K_SOLO;
-    if (int rc = h9g_mon_launch(kind, p1f, &ctx->cfg, solo ? (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK) : pb,
-                                solo ? H9G_YBLOCK : pt, ctx->sc, a, mon))
-      return rc;
-    HIPCHK(hipGetLastError());
+// The year kernel of `shape` over a's slots [c0, cend); mixed: the mixed
+// kind's year, year_ranges' two launches (neither with a second group).
+// mon: the base of the launch's monthly rows; then the shape's monthly kernel.
+static int launch_year(h9g_ctx *ctx, Shape shape, bool mixed, KArgs a, float *mon) {
+  if (mixed) {
+    LaunchRange r[2];
+    const int nr = year_ranges(ctx, r);
+    for (int i = 0; i < nr; i++) {
+      a.c0 = r[i].c0;
+      a.cend = a.bend = a.split = r[i].cend;
+      if (int rc = launch_year(ctx, r[i].shape, false, a, mon)) return rc;
+    }
     return 0;
   }
-  switch (kind) {
-    case K_SOLO:   // (no second group on the solo kernel: [c0, cend) is the launch)
-      H9G_DISPATCH(ctx, h9g_solo_kernel, (unsigned)(((size_t)(a.cend - a.c0) + H9G_YBLOCK - 1) / H9G_YBLOCK), H9G_YBLOCK,
-                   ctx->sc, a);
-      break;
-    case K_MIXED: {
-      LaunchRange r[2];
-      const int nr = year_ranges(ctx, r);
-      for (int i = 0; i < nr; i++) {
-        a.c0 = r[i].c0;
-        a.cend = a.bend = a.split = r[i].cend;
-        if (int rc = launch_year(ctx, r[i].kind, a, blocks, mon, false)) return rc;
-      }
-      return 0;
-    }
-    case K_PAIR2: H9G_DISPATCH_L10(ctx, h9g_pair2_kernel, pb, pt, ctx->sc, a); break;
-    case K_PAIR11: H9G_DISPATCH(ctx, h9g_pair11_kernel, pb, pt, ctx->sc, a); break;
-    case K_PAIR1:
-#if H9G_P1_FRONT
-      if (p1f) {
-        H9G_DISPATCH(ctx, h9g_pair1f_kernel, pb, pt, ctx->sc, a);
-        break;
-      }
-#endif
-      H9G_DISPATCH(ctx, h9g_pair1_kernel, pb, pt, ctx->sc, a);
-      break;
-    default: H9G_DISPATCH(ctx, h9g_pair_kernel, pb, pt, ctx->sc, a); break;
-  }
+  if (int rc = mon ? h9g_mon_launch(shape, &ctx->cfg, ctx->sc, a, mon)
+                   : launch_shape<false>(shape, ctx->cfg, ctx->sc, a, nullptr))
+    return rc;
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// h9g_sort_kernel over slots [c0, cend) in workgroups of cpb cells, of the
+// cells `list` (null: the slots' own numbers) with state st and STOP rows err.
+static int sort_slots(h9g_ctx *ctx, int c0, int cend, int cpb, const float *st, const int *err, const int *list) {
+  return geo_dispatch(ctx->cfg, [&](auto L, auto g) {
+    h9g_sort_kernel<L, decltype(g)><<<H9G_NXCD, H9G_SORT_THREADS, 0, ctx->sc>>>(
+        (int)ctx->n, c0, cend, cpb, st, err, ctx->d_hist, ctx->hist_nsub, ctx->d_perm, list, g);
+    return 0;
+  });
 }
 
 static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
@@ -2029,10 +1443,11 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   a.iostride = ios;
   a.raw = ys.probe ? 1 : 0;
   const Kind kind = d_list && !ys.bulk ? list_kind(ctx, m) : ctx->kind;
-  const KindInfo ki = kind_info(kind);
   const size_t ncells = d_list ? (size_t)m : ctx->n;
-  // the launch's shape, decided here once (the one-column kernel carries no second group: ncells is the launch)
-  const bool p1f = kind == K_PAIR1 && pair1_front(ncells);
+  // the launch's shape (the mixed kind: its pair part's), decided here once
+  // (the one-column kernel carries no second group: ncells is the launch)
+  const Shape shape = year_shape(kind, ncells);
+  const ShapeInfo si = shape_info(shape);
   // slot-ordered forcing and annual sums (row stride ios: the cells plus a
   // second group's slack)
   if (d_list || ctx->sort) {
@@ -2044,11 +1459,11 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   // the second group from the first whole wave after the first group's
   // cells: its slots of d_perm (in h9g_sort_kernel's order over its own
   // state), then its year's forcing into them
-  auto second_group = [&](int base, int pcpb) -> int {
-    const int split = (int)round_up((size_t)base, (size_t)ki.wave_cols);
+  const int pcpb = si.block_cells();
+  auto second_group = [&](int base) -> int {
+    const int split = (int)round_up((size_t)base, (size_t)si.wave_cols);
     HIPCHK(hipMemcpyAsync(ctx->d_perm2 + split, ys.h2, sizeof(int) * ys.k2, hipMemcpyHostToDevice, ctx->sc));
-    H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, split, split + ys.k2, pcpb, ys.st2,
-                 ys.err2, ctx->d_hist, ctx->hist_nsub, ctx->d_perm, ctx->d_perm2);
+    if (int rc = sort_slots(ctx, split, split + ys.k2, pcpb, ys.st2, ys.err2, ctx->d_perm2)) return rc;
     h9g_perm_forcing_kernel<<<perm_forcing_blocks(split, split + ys.k2, pcpb, nt2), 256, 0, ctx->sc>>>(
         split, split + ys.k2, pcpb, nt2, n, a.fvar, ios, dvar, ctx->d_perm, h9g_forcing_slot(ctx, ys.slot2),
         ctx->d_forc_s);
@@ -2061,20 +1476,18 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     return 0;
   };
   if (d_list) {
-    const int pcpb = launch_block_cells(kind, p1f);
     a.perm = d_list;
     if (ctx->sort && kind != K_PAIR1) {
       // the list in h9g_sort_kernel's order (its waves' columns take the
       // same branches), into d_perm, free between every-cell launches
-      H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, 0, m, pcpb, a.st, a.err, ctx->d_hist,
-                   ctx->hist_nsub, ctx->d_perm, d_list);
+      if (int rc = sort_slots(ctx, 0, m, pcpb, a.st, a.err, d_list)) return rc;
       a.perm = ctx->d_perm;
     }
     h9g_perm_forcing_kernel<<<perm_forcing_blocks(0, m, pcpb, nt), 256, 0, ctx->sc>>>(
         0, m, pcpb, nt, n, a.fvar, ios, dvar, a.perm, a.forc, ctx->d_forc_s);
     HIPCHK(hipGetLastError());
     if (two)
-      if (int r = second_group(m, pcpb)) return r;
+      if (int r = second_group(m)) return r;
     a.forc = ctx->d_forc_s;
     a.annual = ctx->d_ann_s;
     a.sorted_io = 1;
@@ -2082,19 +1495,18 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     LaunchRange r[2];
     const int nr = year_ranges(ctx, r);
     for (int i = 0; i < nr; i++)
-      H9G_DISPATCH(ctx, h9g_sort_kernel, H9G_NXCD, H9G_SORT_THREADS, ctx->sc, n, r[i].c0, r[i].cend, r[i].cpb, ctx->d_st,
-                   ctx->d_err, ctx->d_hist, ctx->hist_nsub, ctx->d_perm, nullptr);
+      if (int rc = sort_slots(ctx, r[i].c0, r[i].cend, r[i].cpb(), ctx->d_st, ctx->d_err, nullptr)) return rc;
     HIPCHK(hipGetLastError());
     a.perm = ctx->d_perm;
 #if !defined(H9G_DUMP_AQ)                 // (that record is indexed by the annual array's cell)
     // forcing and annual sums in slot order for the year kernel, per launch
     // range with its workgroup size, as the sort above
     for (int i = 0; i < nr; i++)
-      h9g_perm_forcing_kernel<<<perm_forcing_blocks(r[i].c0, r[i].cend, r[i].cpb, nt), 256, 0, ctx->sc>>>(
-          r[i].c0, r[i].cend, r[i].cpb, nt, n, a.fvar, ios, dvar, ctx->d_perm, a.forc, ctx->d_forc_s);
+      h9g_perm_forcing_kernel<<<perm_forcing_blocks(r[i].c0, r[i].cend, r[i].cpb(), nt), 256, 0, ctx->sc>>>(
+          r[i].c0, r[i].cend, r[i].cpb(), nt, n, a.fvar, ios, dvar, ctx->d_perm, a.forc, ctx->d_forc_s);
     HIPCHK(hipGetLastError());
     if (two)
-      if (int rc = second_group(n, ki.block_cells)) return rc;
+      if (int rc = second_group(n)) return rc;
     a.forc = ctx->d_forc_s;
     a.annual = ctx->d_ann_s;
     a.sorted_io = 1;
@@ -2104,10 +1516,8 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   // the monthly rows, addressed as a.annual
   float *const mon_a = !mon ? nullptr : a.sorted_io ? ctx->d_mon_s : ctx->d_mon;
   // workgroups of the launch (the pair part's, for the mixed kind)
-  const size_t per_block = (size_t)launch_block_cells(kind, p1f);
-  const size_t blocks = kind == K_MIXED ? (ctx->n - ctx->n_solo + per_block - 1) / per_block
-                                        : ((size_t)a.cend + per_block - 1) / per_block;
-  if (ki.pair) {
+  const size_t blocks = shape_blocks(shape, kind == K_MIXED ? ctx->n - ctx->n_solo : (size_t)a.cend);
+  if (si.pair) {
     // the pair kernels' day-snapshot blocks, one per workgroup of the launch
     const size_t need = std::max<size_t>(blocks, 1) * PairStore<8, H9G_PLANES>::GBLOCK;
     if (ctx->sv_bytes < need) {
@@ -2126,7 +1536,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   }
   a.pace = ctx->d_pace;
   a.epoch = ++ctx->epoch;
-  a.prio_mode = pace_mode(ctx, kind, blocks);
+  a.prio_mode = pace_mode(ctx, shape, blocks);
 #if defined(H9G_STAMPS)
   {  // one record of 8 words per wave of the launch
     const size_t words = (size_t)8 * H9G_PWAVES * (blocks + 1);
@@ -2138,7 +1548,7 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     }
     HIPCHK(hipMemsetAsync(ctx->d_stamps, 0, sizeof(unsigned) * words, ctx->sc));
     a.stamps = ctx->d_stamps;
-    ctx->stamp_p1f = p1f;
+    ctx->stamp_shape = shape;
     ctx->stamp_blocks = blocks;
   }
 #endif
@@ -2171,10 +1581,10 @@ static int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   ctx->ev_kind[e] = ys.probe ? K_PROBE : kind;
   ctx->ev_cells[e] = (int64_t)ncells + (two ? ys.k2 : 0);
   HIPCHK(hipEventRecord(ctx->ev0[e], ctx->sc));
-  if (int r = launch_year(ctx, kind, a, blocks, mon_a, p1f)) return r;
+  if (int r = launch_year(ctx, shape, kind == K_MIXED, a, mon_a)) return r;
   // a one-column context's name is the kernel its last year ran on (the
   // launch record of the shape; until a year runs, h9g_create's)
-  if (kind == K_PAIR1 && ctx->kind == K_PAIR1) ctx->kname = pair1_name(ctx, p1f);
+  if (kind == K_PAIR1 && ctx->kind == K_PAIR1) ctx->kname = year_kernel_name(ctx, kind, ncells);
   HIPCHK(hipEventRecord(ctx->ev1[e], ctx->sc));
   HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot], ctx->sc));
   if (two) HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot2], ctx->sc));
@@ -2283,7 +1693,11 @@ static int daily_launch(h9g_ctx *ctx, const float *st, const float *guess, const
   a.err = err;
   a.yrs = ctx->d_fyrs + k0;
   a.out = ctx->d_daily + day0 * H9G_NDAILY * (size_t)nsel;
-  H9G_DISPATCH(ctx, h9g_focus_kernel, (unsigned)((nsel + 63) / 64), 64, ctx->sc, a);
+  if (int rc = geo_dispatch(ctx->cfg, [&](auto L, auto g) {
+        h9g_focus_kernel<L, decltype(g)><<<(unsigned)((nsel + 63) / 64), 64, 0, ctx->sc>>>(a, g);
+        return 0;
+      }))
+    return rc;
   HIPCHK(hipGetLastError());
   for (int y = 0; y < ny; y++) ctx->daily_nt.push_back(days_in_year(jyear0 + y));
   return 0;
@@ -3086,7 +2500,7 @@ int h9g_sync(h9g_ctx *ctx) {
   if (int r = fold_events(ctx)) return r;
 #if defined(H9G_STAMPS)
   if (ctx->d_stamps && (ctx->kind == K_PAIR || ctx->kind == K_PAIR11 || ctx->kind == K_PAIR1)) {   // mean shader cycles per wave and substep, by phase
-    const size_t cw = (size_t)kind_info(ctx->kind).wave_cols, nw = (ctx->n + cw - 1) / cw;
+    const size_t cw = (size_t)shape_info(kind_info(ctx->kind).shape).wave_cols, nw = (ctx->n + cw - 1) / cw;
     std::vector<unsigned> st(8 * nw);
     HIPCHK(hipMemcpy(st.data(), ctx->d_stamps, sizeof(unsigned) * 8 * nw, hipMemcpyDeviceToHost));
     double sum[8] = {0}, tot = 0;
@@ -3096,7 +2510,7 @@ int h9g_sync(h9g_ctx *ctx) {
     fprintf(stderr, "h9g stamps (cycles/wave/substep):");
     for (int k = 0; k < 8; k++) { fprintf(stderr, " p%d=%.0f", k, sum[k] / steps); tot += sum[k]; }
     fprintf(stderr, " total=%.0f\n", tot / steps);
-    if (ctx->stamp_p1f) {
+    if (shape_info(ctx->stamp_shape).front()) {
       // the two-wave shape, by the launch's own record: p1 above is the main
       // wave's wait at barrier 2; the front waves' records follow the grid's
       // main waves' (pair_body: one main wave per workgroup)
@@ -3235,7 +2649,14 @@ int h9g_run_site(h9g_ctx *ctx, int nday, const float *sub, const float *daily, c
   if (e == hipSuccess) e = hipMemcpy(buf + nsub, daily, sizeof(float) * nd, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(buf + nsub + nd, lai, sizeof(float) * nl, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    H9G_DISPATCH(ctx, h9g_site_kernel, (unsigned)((n + 63) / 64), 64, ctx->sc, a);
+    rc = geo_dispatch(ctx->cfg, [&](auto L, auto g) {
+      h9g_site_kernel<L, decltype(g)><<<(unsigned)((n + 63) / 64), 64, 0, ctx->sc>>>(a, g);
+      return 0;
+    });
+    if (rc) {
+      (void)hipFree(buf);
+      return rc;
+    }
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->sc);
@@ -3639,4 +3060,3 @@ float h9g_host_powf(float x, float y) {
 }
 
 }  // extern "C"
-#endif  // H9G_ISA_ONLY

@@ -280,7 +280,7 @@ def test_shard_invariance_and_determinism():
 def test_spare_lanes_in_ragged_waves(L, nisurf, kernel, monkeypatch):
     """The helper lanes of a pair-kernel wave (20 with 22 columns, 42 with
     11) evaluate the pairs' first layer slots and mirror a pair lane
-    elsewhere (h9g.hip pair_body).  Waves with 1, 3, 9 and 22 + 1 columns
+    elsewhere (h9g_year.h pair_body).  Waves with 1, 3, 9 and 22 + 1 columns
     (the mirror wraps; a second, one-column wave) give the same bits for
     every cell as the same cells inside a 1,500-cell run of full waves."""
     monkeypatch.setenv("H9G_KERNEL", kernel)
@@ -310,6 +310,34 @@ def test_masked_waves_with_spare_lanes(monkeypatch):
                 nyears=inp["nyears"], grow_on=bool(inp["grow_on"]), state0=inp["state0"], stop_on_error=False)
     assert np.isnan(out["annual"][:, :, :44]).all()
     assert same_bits(out["annual"][:, :, 44:], exp["annual"][:, :, 44:])
+
+
+@pytest.mark.parametrize("kernel,split,L,nisurf,cells,want", [
+    ("pair", None, 8, 48, 3, "h9g_pair_kernel<8,GeoC<8,48>>"),
+    ("pair11", None, 8, 48, 3, "h9g_pair11_kernel<8,GeoC<8,48>>"),
+    ("solo", None, 8, 48, 3, "h9g_solo_kernel<8,GeoC<8,48>>"),
+    ("pair", None, 8, 12, 3, "h9g_pair_kernel<8,GeoR>"),
+    ("pair2", None, 10, 24, 30, "h9g_pair2_kernel<10,GeoC<10,24>>"),
+    ("mixed", "17", 10, 24, 30, "h9g_solo_kernel<10,GeoC<10,24>>+h9g_pair_kernel<10,GeoC<10,24>>"),
+    ("pair2", None, 8, 48, 3, "h9g_pair_kernel<8,GeoC<8,48>>"),      # pair2 is L = 10 only: the default kernel
+])
+def test_kernel_name_of_every_kind(kernel, split, L, nisurf, cells, want, monkeypatch):
+    """h9g_kernel_name of a context of each kind and geometry variant (the
+    one-column kernel's names: test_gpu_pair1_front.py), before any year and
+    again after a year has run."""
+    monkeypatch.setenv("H9G_KERNEL", kernel)
+    if split is not None:
+        monkeypatch.setenv("H9G_SPLIT", split)
+    gid = synth.land_cells()[::331][:cells]
+    with h.Context(gid.size, synth.ZI_L8 if L == 8 else synth.ZI_L10, nlayers=L, nisurf=nisurf, grow_on=False) as ctx:
+        assert ctx.kernel_name() == want
+        ctx.set_cells(gid, synth.cell_lat(gid, synth.NX05, synth.NY05))
+        ctx.synth_params(synth.SEED)
+        ctx.init_state()
+        ctx.synth_forcing(0, synth.SEED, synth.year_day0(1903), synth.days_in_year(1903))
+        ctx.run_year(0, 1903)
+        ctx.sync()
+        assert ctx.kernel_name() == want
 
 
 @pytest.mark.parametrize("kernel", ["pair", "solo"])

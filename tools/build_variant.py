@@ -15,7 +15,7 @@ from hybrid9_amd import build as hb  # noqa: E402
 
 def main() -> None:
     tag, extra = sys.argv[1], sys.argv[2:]
-    if "--c2" in extra:      # config-2 instantiation only (h9g.hip H9G_ONLY_C2): ~1 min
+    if "--c2" in extra:      # config-2 instantiation only (h9g_year.h geo_dispatch, H9G_ONLY_C2): ~1 min
         extra = [e for e in extra if e != "--c2"] + ["-DH9G_ONLY_C2"]
     out = hb.OUT.with_name(f"libh9g_{tag}.so")
     cmd = [hb.hipcc(), f"--offload-arch={hb.ARCH}", *hb.FLAGS, *extra, hb.id_flag(extra), str(hb.SRC),

@@ -102,7 +102,7 @@ def kernels_of_dis(text: str) -> dict[str, list[str]]:
         if cur is None or not line.startswith(("\t", " ")):
             continue
         ln = line.split("//", 1)[0].strip()
-        if ln:
+        if ln and ln != "...":      # ("...": zero padding the disassembler elides, after a unit's last kernel)
             cur.append(re.sub(r"\s+", " ", ln))
     return {k: v for k, v in out.items() if v}
 
@@ -143,7 +143,8 @@ def opcodes(lines: list[str], fold: bool) -> collections.Counter:
     return c
 
 
-LIT = re.compile(r"(?<![\w.])(0x[0-9a-fA-F]+|-?\d+)(?![\w.])")
+# (a symbol's pc-relative reference in an assembly is the address literal of a disassembly)
+LIT = re.compile(r"(?<![\w.])(0x[0-9a-fA-F]+|-?\d+|[\w$.]+@rel32@(?:lo|hi))(?![\w.])")
 
 
 def literal_only(a: list[str], b: list[str]) -> list[tuple[int, str, str]] | None:

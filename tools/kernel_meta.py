@@ -27,7 +27,8 @@ BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def code_objects(lib: Path, tmp: Path) -> list[Path]:
     """The gfx950 code object of every device translation unit of the library
-    (the year kernels' and the monthly kernels'): .hip_fatbin holds one
+    (h9g.hip's and h9g_mon.hip's, each with its own instantiations of
+    h9g_year.h's kernels): .hip_fatbin holds one
     offload bundle per unit, one after the other."""
     fat = tmp / "fat.bin"
     subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib), str(tmp / "x.so")],
