@@ -134,6 +134,8 @@ def lib() -> C.CDLL:
         "h9g_write_axy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _I64P, _FP]),
         "h9g_write_mxy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _I64P, C.c_int, C.c_int,
                                        _FP]),
+        "h9g_write_mxy_nc_evap": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _I64P, C.c_int,
+                                            C.c_int, _FP]),
         "h9g_nc_forcing_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _I64P,
                                           C.c_int, C.c_int, _FP]),
         "h9g_nc_ntimes": (C.c_int, [C.c_char_p]),
@@ -149,6 +151,7 @@ def lib() -> C.CDLL:
         "h9g_set_daily": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32)]),
         "h9g_get_daily": (C.c_int, [vp, C.c_int, _FP]),
         "h9g_set_monthly": (C.c_int, [vp, C.c_int]),
+        "h9g_set_evap": (C.c_int, [vp, C.c_int]),
         "h9g_get_monthly": (C.c_int, [vp, C.c_int, _FP]),
         "h9g_host_expf": (C.c_float, [C.c_float]),
         "h9g_host_powf": (C.c_float, [C.c_float, C.c_float]),
@@ -490,6 +493,17 @@ class Context:
         STOP records and daily lines are the same bit for bit either way."""
         _check(self._lib.h9g_set_monthly(self._h, int(bool(on))), "h9g_set_monthly")
 
+    def set_evap(self, on: bool = True):
+        """Turns evapotranspiration recording on or off (h9g_set_evap; off by
+        default).  With it on every year launch runs the ET year kernels, and
+        row evap (3) of the annual means and of the month-end snapshots is the
+        year's evaporation sum, sum over the substeps of (qflx_evap_grnd +
+        qflx_tran_veg_col) * dt in float32, in mm: divided by nt * nisurf in
+        the annual means like row rnf, as it stands in a snapshot.  Every
+        other row, the state, the STOP records and the daily lines are the
+        same bits either way."""
+        _check(self._lib.h9g_set_evap(self._h, int(bool(on))), "h9g_set_evap")
+
     def get_monthly(self, k: int = 0) -> np.ndarray:
         """The month-end snapshots of year k (0-based) of the last run_year
         (k = 0) or ordered call: (12, 12+L, ncell) float32, the undivided
@@ -616,18 +630,20 @@ def write_axy_nc(path, annual, gid, zc, nx: int = 720, ny: int = 360):
                                   gid.ctypes.data_as(_I64P), _fp(annual)), "h9g_write_axy_nc")
 
 
-def write_mxy_nc(path, snapshots, gid, zc, jyear: int, nisurf: int, nx: int = 720, ny: int = 360):
+def write_mxy_nc(path, snapshots, gid, zc, jyear: int, nisurf: int, nx: int = 720, ny: int = 360, evap=False):
     """One year of monthly means, derived as ``monthly_means`` derives them
     from the month-end snapshots (12, 12+L, ncell) of the cells gid, to
     mxyYYYY.nc: write_axy_nc's variables under a leading dimension month
-    (h9g_write_mxy_nc; netCDF classic)."""
+    (h9g_write_mxy_nc; netCDF classic).  evap: the snapshots of an ET run
+    (Context.set_evap), row evap divided like row rnf (h9g_write_mxy_nc_evap)."""
     snapshots = np.ascontiguousarray(snapshots, dtype=np.float32)
     gid = np.ascontiguousarray(gid, dtype=np.int64)
     zc = np.ascontiguousarray(zc, dtype=np.float32)
     L = snapshots.shape[1] - 12
     assert snapshots.shape == (NMONTHS, 12 + L, gid.size) and zc.size == L
-    _check(lib().h9g_write_mxy_nc(str(path).encode(), nx, ny, L, _fp(zc), gid.size, gid.ctypes.data_as(_I64P),
-                                  int(jyear), int(nisurf), _fp(snapshots)), "h9g_write_mxy_nc")
+    name = "h9g_write_mxy_nc_evap" if evap else "h9g_write_mxy_nc"
+    _check(getattr(lib(), name)(str(path).encode(), nx, ny, L, _fp(zc), gid.size, gid.ctypes.data_as(_I64P),
+                                int(jyear), int(nisurf), _fp(snapshots)), name)
 
 
 def month_ends(jyear: int) -> np.ndarray:
@@ -638,12 +654,14 @@ def month_ends(jyear: int) -> np.ndarray:
     return e
 
 
-def monthly_means(snapshots, jyear: int, nisurf: int) -> np.ndarray:
+def monthly_means(snapshots, jyear: int, nisurf: int, evap=False) -> np.ndarray:
     """Monthly means from one year's month-end snapshots (12, 12+L, ncell)
     (Context.get_monthly): in float64, (S[m] - S[m-1]) / days_m with
     S[-1] = 0, rounded to float32; the divisor is days_m * nisurf for rnf
     (row 2) and 1 for npp (row 0, a monthly total, as the annual row is a
-    yearly total).  Row evap (3) is the reference's zero.  Derived from the
+    yearly total).  Row evap (3) is the reference's zero; evap: the
+    snapshots of an ET run (Context.set_evap), whose row evap is a sum over
+    the substeps like rnf: its divisor is then days_m * nisurf too.  Derived from the
     reference's f32 running sums: deterministic, but not a reference
     quantity (the reference writes annual means only)."""
     s = np.asarray(snapshots, dtype=np.float32).astype(np.float64)
@@ -654,6 +672,8 @@ def monthly_means(snapshots, jyear: int, nisurf: int) -> np.ndarray:
     div = np.repeat(days[:, None], s.shape[1], axis=1)
     div[:, 0] = 1.0
     div[:, 2] = days * float(nisurf)
+    if evap:
+        div[:, 3] = days * float(nisurf)
     return (d / div[:, :, None]).astype(np.float32)
 
 
@@ -670,7 +690,7 @@ def decades(year0: int, nyears: int):
 
 def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                    state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None,
-                   monthly=False):
+                   monthly=False, evap=False):
     """``run`` in the reference's own cell order (smp carried from cell to
     cell, cells in the given order; chains: a reference rank per cell, each
     rank its own chain, shard.reference_blocks).  pipelined: one
@@ -682,7 +702,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
     line is recorded (Context.set_daily) -> out["daily"] (ndays, 11, nsel); the
     decades then run one after another.  monthly: the month-end snapshots
     (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n); the decades
-    stay overlapped."""
+    stay overlapped.  evap: evapotranspiration recording (Context.set_evap):
+    row evap of annual and monthly is the year's evaporation sum."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device,
@@ -693,6 +714,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             ctx.set_daily(daily_cells)
         if monthly:
             ctx.set_monthly(True)
+        if evap:
+            ctx.set_evap(True)
         if state0 is None:
             ctx.init_state()
         else:
@@ -720,7 +743,7 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
         # goes on with the other cells; the decade-by-decade form stops there
         return run_cell_order(zi=zi, params=params, forcing=forcing, nisurf=nisurf, year0=year0, nyears=nyears,
                               grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False,
-                              daily_cells=daily_cells, monthly=monthly)
+                              daily_cells=daily_cells, monthly=monthly, evap=evap)
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device, nslots=10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
@@ -728,6 +751,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             ctx.set_daily(daily_cells)
         if monthly:
             ctx.set_monthly(True)
+        if evap:
+            ctx.set_evap(True)
         if state0 is None:
             ctx.init_state()
         else:
@@ -763,7 +788,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
 
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
-        state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False):
+        state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False,
+        evap=False):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -774,7 +800,10 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     go on.  ``errors`` holds every cell's STOP record (Context.get_errors).
     daily_cells: the cells whose daily line is recorded (Context.set_daily)
     -> out["daily"] (ndays of the years run, 11, nsel).  monthly: the month-end
-    snapshots (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n)."""
+    snapshots (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n).
+    evap: evapotranspiration recording (Context.set_evap): row evap (3) of
+    annual and monthly is the year's evaporation sum instead of the
+    reference's zero."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device) as ctx:
@@ -787,6 +816,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             ctx.set_daily(daily_cells)
         if monthly:
             ctx.set_monthly(True)
+        if evap:
+            ctx.set_evap(True)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
         d0, rc, err, daily = 0, 0, None, []

@@ -17,8 +17,9 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "csrc" / "h9g.hip"
 SRC_MON = HERE / "csrc" / "h9g_mon.hip"     # the monthly kernels: h9g_year.h's kernels with the Months policy
+SRC_ET = HERE / "csrc" / "h9g_et.hip"       # the ET kernels: the same kernels with the EvapProf and MonthsEt policies
 SRC_IO = HERE / "csrc" / "h9g_io.cpp"       # host-only NetCDF I/O
-DEPS = [SRC, SRC_MON, SRC_IO, HERE / "csrc" / "h9g_year.h", HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
+DEPS = [SRC, SRC_MON, SRC_ET, SRC_IO, HERE / "csrc" / "h9g_year.h", HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
         HERE / "csrc" / "h9g_synth.h", HERE / "csrc" / "h9g_geo.h",
         HERE / "csrc" / "h9g_pair.h", HERE / "csrc" / "h9g_expr.h", HERE / "csrc" / "h9g_rows.h",
         HERE / "csrc" / "h9g_io.h",
@@ -71,10 +72,11 @@ def _run(cmd, verbose):
 
 
 def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
-    """Compiles the three translation units to objects (h9g.hip with the year
-    kernels and everything else on the device, and h9g_mon.hip with the
-    monthly kernels, ~4 minutes each and side by side: both include
-    h9g_year.h; and the host-only NetCDF I/O, seconds; each only when its own
+    """Compiles the four translation units to objects (h9g.hip with the year
+    kernels and everything else on the device, h9g_mon.hip with the monthly
+    kernels and h9g_et.hip with the ET kernels, ~4 minutes each and side by
+    side: all three include h9g_year.h; and the host-only NetCDF I/O, seconds,
+    so four compilers at the most; each only when its own
     inputs changed, keyed by their digest) and links libh9g.so."""
     if not force and up_to_date():
         return OUT
@@ -84,9 +86,10 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
     import hashlib
     flags = [f"--offload-arch={ARCH}", *FLAGS, *extra]
     objs, jobs = [], []
-    hdrs = [d for d in DEPS if d not in (SRC, SRC_IO, SRC_MON)]
+    hdrs = [d for d in DEPS if d not in (SRC, SRC_IO, SRC_MON, SRC_ET)]
     # h9g_build_id lives in the I/O unit: only it gets the digest flag
     for src, deps, idf in ((SRC, [SRC, *hdrs], []), (SRC_MON, [SRC_MON, *hdrs], []),
+                           (SRC_ET, [SRC_ET, *hdrs], []),
                            (SRC_IO, [SRC_IO, HERE / "csrc" / "h9g_io.h", DEPS[-1]], [id_flag(extra)])):
         flags_u = flags + idf
         hs = hashlib.sha256(" ".join(flags_u).encode())

@@ -807,6 +807,9 @@ struct h9g_ctx {
   int mon_base = 0;               // first year of the running ordered call there
   int mon_years = 0;              // years recorded by the last call (0: none)
   bool mon_in_ret = false;        // ... in d_mon_ret (an ordered call) or d_mon (h9g_run_year)
+  // evapotranspiration output (h9g_set_evap; the ET kernels): row evap of the
+  // annual and monthly rows is the year's evaporation sum.  No buffer of its own.
+  int evap = 0;
 };
 
 static void ord_free(h9g_ctx *ctx);
@@ -837,7 +840,10 @@ static std::string year_kernel_name(const h9g_ctx *ctx, int kind, size_t cells) 
   const GeoKind gk = geo_kind(ctx->cfg);
   const std::string L = std::to_string(ctx->L);
   const std::string targs = "<" + L + "," + (gk == GEO_R ? "GeoR" : "GeoC<" + L + "," + std::to_string((int)gk) + ">") + ">";
-  auto name = [&](int k) { return shape_info(year_shape(k, cells)).name + targs; };
+  auto name = [&](int k) {
+    const ShapeInfo si = shape_info(year_shape(k, cells));
+    return (ctx->evap ? si.et_name : si.name) + targs;
+  };
   return kind == K_MIXED ? name(K_SOLO) + "+" + name(K_PAIR) : name(kind);
 }
 
@@ -1355,6 +1361,7 @@ static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
 // The year kernel of `shape` over a's slots [c0, cend); mixed: the mixed
 // kind's year, year_ranges' two launches (neither with a second group).
 // mon: the base of the launch's monthly rows; then the shape's monthly kernel.
+// An ET context (h9g_set_evap): the shape's ET kernel, with mon or without.
 static int launch_year(h9g_ctx *ctx, Shape shape, bool mixed, KArgs a, float *mon) {
   if (mixed) {
     LaunchRange r[2];
@@ -1366,8 +1373,9 @@ static int launch_year(h9g_ctx *ctx, Shape shape, bool mixed, KArgs a, float *mo
     }
     return 0;
   }
-  if (int rc = mon ? h9g_mon_launch(shape, &ctx->cfg, ctx->sc, a, mon)
-                   : launch_shape<false>(shape, ctx->cfg, ctx->sc, a, nullptr))
+  if (int rc = ctx->evap ? h9g_et_launch(shape, &ctx->cfg, ctx->sc, a, mon)
+               : mon     ? h9g_mon_launch(shape, &ctx->cfg, ctx->sc, a, mon)
+                         : launch_shape<V_PLAIN>(shape, ctx->cfg, ctx->sc, a, nullptr))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -1779,6 +1787,27 @@ int h9g_set_monthly(h9g_ctx *ctx, int on) {
   HIPCHK(hipStreamSynchronize(ctx->sc));
   ctx->monthly = on ? 1 : 0;
   ctx->mon_years = 0;
+  return 0;
+}
+
+// The context's name follows (h9g_kernel_name: the ET kernels').  The day-1
+// probes of the cell order then run the ET kernels too: their rows are the
+// running sums (KArgs::raw), so h9g_probe_cmp_kernel compares the first
+// day's evaporation with the other rows.
+int h9g_set_evap(h9g_ctx *ctx, int on) {
+  if (!ctx) return H9G_EINVAL;
+#if defined(H9G_STAMPS)
+  if (on) return H9G_EINVAL;   // (as h9g_set_monthly)
+#endif
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  if (ctx->evap != (on ? 1 : 0)) {
+    ctx->evap = on ? 1 : 0;
+    // (a one-column context's name is the shape of its last year: renamed in place)
+    const std::string from = on ? "_kernel" : "_et_kernel", to = on ? "_et_kernel" : "_kernel";
+    for (size_t p = 0; (p = ctx->kname.find(from, p)) != std::string::npos; p += to.size())
+      ctx->kname.replace(p, from.size(), to);
+  }
   return 0;
 }
 

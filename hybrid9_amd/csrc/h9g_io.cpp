@@ -817,9 +817,10 @@ int h9g_write_axy_nc(const char *path, int nx, int ny, int nlayers, const float 
 // (h9g_get_monthly: the year's running sums, undivided), axyYYYY.nc's fields
 // under a leading dimension month.  mean = (S[m] - S[m-1]) / days_m in double
 // (S[-1] = 0), rounded to float; the divisor is days_m * nisurf for runoff and
-// 1 for net primary production (a monthly total).
-int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers, const float *zc, int ncell,
-                     const int64_t *gid, int jyear, int nisurf, const float *snapshots) {
+// 1 for net primary production (a monthly total).  evap: row evaporation is
+// an ET run's sum over the substeps (h9g_set_evap), divided like runoff.
+static int write_mxy(const char *path, int nx, int ny, int nlayers, const float *zc, int ncell, const int64_t *gid,
+                     int jyear, int nisurf, const float *snapshots, bool evap) {
   if (!path || nx <= 0 || ny <= 0 || nlayers < 1 || nlayers > H9G_LMAX || ncell < 0 || nisurf < 1 ||
       (ncell && (!gid || !snapshots)))
     return H9G_EINVAL;
@@ -831,12 +832,20 @@ int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers, const float 
   std::vector<float> mean((size_t)H9G_NMONTHS * rows * ncell);
   for (int m = 0; m < H9G_NMONTHS; m++)
     for (int k = 0; k < rows; k++) {
-      const double div = k == 0 ? 1.0 : k == 2 ? (double)mdays[m] * (double)nisurf : (double)mdays[m];
+      const double div = k == 0 ? 1.0 : k == 2 || (evap && k == 3) ? (double)mdays[m] * (double)nisurf : (double)mdays[m];
       const float *s1 = snapshots + ((size_t)m * rows + k) * ncell, *s0 = m ? s1 - (size_t)rows * ncell : nullptr;
       float *o = mean.data() + ((size_t)m * rows + k) * ncell;
       for (int c = 0; c < ncell; c++) o[c] = (float)(((double)s1[c] - (s0 ? (double)s0[c] : 0.0)) / div);
     }
   return write_xy_nc(path, nx, ny, nlayers, zc, ncell, gid, mean.data(), H9G_NMONTHS, "g[DM]/m^2/month");
+}
+int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers, const float *zc, int ncell,
+                     const int64_t *gid, int jyear, int nisurf, const float *snapshots) {
+  return write_mxy(path, nx, ny, nlayers, zc, ncell, gid, jyear, nisurf, snapshots, false);
+}
+int h9g_write_mxy_nc_evap(const char *path, int nx, int ny, int nlayers, const float *zc, int ncell,
+                          const int64_t *gid, int jyear, int nisurf, const float *snapshots) {
+  return write_mxy(path, nx, ny, nlayers, zc, ncell, gid, jyear, nisurf, snapshots, true);
 }
 
 // READ_PGF.f90 + READ_NET_CDF_3DR.f90 for the cells of a context: days

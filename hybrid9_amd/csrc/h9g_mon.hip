@@ -19,5 +19,5 @@ int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t st
 }
 
 int h9g_mon_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon) {
-  return launch_shape<true>(shape, *cfg, stream, a, mon);
+  return launch_shape<V_MON>(shape, *cfg, stream, a, mon);
 }

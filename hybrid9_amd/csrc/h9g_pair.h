@@ -27,6 +27,8 @@
 // Stores: PairStore (device LDS, [row][lane] with the pair's layers
 // interleaved over its two columns) and FlatStore (host, flat per cell).
 #pragma once
+#include <type_traits>
+
 #include "h9g_step.h"
 #include "h9g_expr.h"
 #if !defined(__HIPCC__) && !defined(__HIP__)
@@ -65,9 +67,11 @@ enum : int {
   PS_DRS = PS_DR0 + 4 * DRP_N,         //   (c.lo s.lo c.hi s.hi), then shared doubles (lo hi)
   PS_SVZWT = PS_DR0 + 2 * DR_N,        // day snapshot for the exact re-run (sv_* of the store)
   PS_SVWA, PS_SVRNF, PS_SVERR, PS_SVNS,
+  PS_SVEVAP,                           // (the ET kernels only: EvapProf)
   PS_N
 };
-enum : int { SV_ZWT = 0, SV_WA, SV_RNF, SV_ERR, SV_NS };   // sv_sc fields (SV_NS: substep of the snapshot)
+// sv_sc fields (SV_NS: substep of the snapshot; SV_EVAP: the evaporation sum, stored and read by the ET kernels only)
+enum : int { SV_ZWT = 0, SV_WA, SV_RNF, SV_ERR, SV_NS, SV_EVAP };
 // canopy/soil pairs share a row, canopy in the even column (see D_NUMC)
 static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_DAY + D_DGRAC) % 2 == 0 &&
                   (PS_DAY + D_DRR) % 2 == 0 && (PS_DAY + D_RAC) % 2 == 0 && PS_DR0 % 2 == 0,
@@ -452,12 +456,13 @@ struct PairStore {
 
 // Device, one lane per column ("solo"): column `lane` of a [row][64] block,
 // every field in the lane's own column; no reciprocal fields, no parking
-// (1054 waves = 5 blocks/CU), day snapshot in LDS.
-template <int L>
+// (1054 waves = 5 blocks/CU), day snapshot in LDS.  EV: one more snapshot
+// field, SV_EVAP (the ET kernels).
+template <int L, bool EV = false>
 struct SoloStore {
   static constexpr bool kRecip = false, kRts = false, kDayRecip = false, kRtsHK = false, kSpare = false, kFront = false;
   static constexpr int NPF = PF_RPSI0 + 2;           // TS..ROOTR, SVH2O, SVSMP
-  static constexpr int NPS = PS_LAI + 5;             // FMAX..DAY, SV*
+  static constexpr int NPS = PS_LAI + 5 + (EV ? 1 : 0);   // FMAX..DAY, SV*
   static constexpr int ROWS = NPF * L + NPS;
   lds_float *b;
   const lds_float *zt;
@@ -524,6 +529,20 @@ struct FluxProf {
   H9K_HD void mark(int) {}
   H9K_HD void flux(float e, float t) { evg = e; tran = t; }
 };
+// The ET kernels' policy (h9g_set_evap): the year's evaporation
+// sum, evap_sum = evap_sum + (qflx_evap_grnd + qflx_tran_veg_col) * dt once a
+// substep (HYBRID9.f90:207-208's expression, in the form of rnf_sum's
+// HYDROLOGY.f90:1282-1283), added where the substep hands the two fluxes over.
+// A substep that ends in a STOP leaves the cell's rows NaN, and one that is
+// re-run exactly takes the sum back from the day snapshot (SV_EVAP), so adding
+// here or after the substep is the same sum.  dt: g.dt().
+struct EvapProf {
+  float sum, dt;
+  H9K_HD void mark(int) {}
+  H9K_HD void flux(float e, float t) { sum = sum + (e + t) * dt; }
+};
+template <class PR>
+constexpr bool kEvap = std::is_same<typename std::remove_reference<PR>::type, EvapProf>::value;
 #if defined(H9G_STAMPS)
 H9K_HD uint64_t stamp_clock() {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1697,6 +1716,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     tran = cs.ho(CS::HO_TRAN);
     evg = cs.ho(CS::HO_EVG);
     qflx_infl = cs.ho(CS::HO_INFL);
+    pr.flux(evg, tran);                  // (the front, skipped here, holds the other roles' call)
     pr.mark(1);
   }
   // :645-650 aquifer node geometry
@@ -2205,7 +2225,8 @@ H9K_HD void save_day(const SP &sp, const CS &cs, const St<L> &s, float rnf_sum, 
 // computing every layer with the full glibc special-case logic.  The fast
 // path's substeps before ns are bit-identical to these, so replaying them
 // reproduces its state exactly.  The snapshot then holds the state after ns.
-template <int L, class G, class CS>
+// EV (the ET kernels): the evaporation sum too, from SV_EVAP and back.
+template <int L, class G, class CS, bool EV = false>
 H9K_RARE int substep_exact_pair(const G *g, CS cs, const uint64_t *e2, const double *l2, int ns) {
   cs.sv_sync();
   St<L> s;
@@ -2219,11 +2240,12 @@ H9K_RARE int substep_exact_pair(const G *g, CS cs, const uint64_t *e2, const dou
   float rnf = cs.sv_sc(SV_RNF), errval = zero;
   MathExact me{{e2, l2}};
   const SplitAll sa;
-  NoProf np;
+  typename std::conditional<EV, EvapProf, NoProf>::type np;
+  if constexpr (EV) np = EvapProf{cs.sv_sc(SV_EVAP), g->dt()};
   int code = 0;
   H9G_EXACT_HOOK((int)cs.sv_sc(SV_NS), ns);
   for (int k = (int)cs.sv_sc(SV_NS); k <= ns && !code; k++)
-    code = hydrology_pair<L, G, MathExact, SplitAll, CS>(*g, cs, sa, s, rnf, errval, me, np);
+    code = hydrology_pair<L, G, MathExact, SplitAll, CS, decltype(np)>(*g, cs, sa, s, rnf, errval, me, np);
   cs.launder();
 #pragma unroll
   for (int i = 1; i <= L; i++) {
@@ -2235,6 +2257,7 @@ H9K_RARE int substep_exact_pair(const G *g, CS cs, const uint64_t *e2, const dou
   cs.sv_set_sc(SV_RNF, rnf);
   cs.sv_set_sc(SV_ERR, errval);
   cs.sv_set_sc(SV_NS, (float)(ns + 1));
+  if constexpr (EV) cs.sv_set_sc(SV_EVAP, np.sum);
   cs.sv_sync();
   return code;
 }
@@ -2287,7 +2310,7 @@ H9K_HD int substep_pair(const G &g, CS cs, const SP &sp, St<L> &s, float &rnf_su
     atomicAdd(&h9g_exact_wave[(blockIdx.x * 4 + (threadIdx.x >> 6)) & 0xffff], 1u);
 #endif
     cs.launder();
-    code = substep_exact_pair<L, G, CS>(&g, cs, T.exp2, T.log2, ns);
+    code = substep_exact_pair<L, G, CS, kEvap<PR>>(&g, cs, T.exp2, T.log2, ns);
     cs.launder();
 #pragma unroll
     for (int i = 1; i <= L; i++) {
@@ -2298,6 +2321,7 @@ H9K_HD int substep_pair(const G &g, CS cs, const SP &sp, St<L> &s, float &rnf_su
     s.wa = cs.sv_sc(SV_WA);
     rnf_sum = cs.sv_sc(SV_RNF);
     errval = cs.sv_sc(SV_ERR);
+    if constexpr (kEvap<PR>) pr.sum = cs.sv_sc(SV_EVAP);
   }
   return code;
 }
@@ -2348,6 +2372,26 @@ struct Months {
     float v[12 + L];
 #pragma unroll
     for (int k = 0; k < 12 + L; k++) v[k] = k == 2 ? rnf_sum : k == 3 ? zero : A[k * as];
+#pragma unroll
+    for (int k = 0; k < 12 + L; k++) o[k * stride] = v[k];
+  }
+};
+
+// MonthsEt: the ET kernels' (EvapProf), with row evap the evaporation sum as
+// it stands, like rnf_sum.  M may be null (ET without monthly recording: one
+// kernel serves both): nothing is stored then, by a wave-uniform test.
+struct MonthsEt {
+  gbl_float *M;
+  size_t stride;
+  template <int L>
+  H9K_HD void day_end(int day, int nt, const gbl_float *A, size_t as, float rnf_sum, float evap_sum) const {
+    if (!M) return;
+    const int m = month_end(day + 1, nt);
+    if (m < 0) return;
+    gbl_float *o = M + (size_t)m * (12 + L) * stride;
+    float v[12 + L];
+#pragma unroll
+    for (int k = 0; k < 12 + L; k++) v[k] = k == 2 ? rnf_sum : k == 3 ? evap_sum : A[k * as];
 #pragma unroll
     for (int k = 0; k < 12 + L; k++) o[k * stride] = v[k];
   }
@@ -2446,7 +2490,11 @@ H9K_HD void front_year_pair(const G &g, CS cs, const SP &sp, const h9m::Tabs &T,
 
 // One calendar year for one cell (HYBRID9.f90:150-290), as cell_year.
 // Park = keep the plant state in the store over the substeps (register
-// relief for the 168-VGPR pair kernel).  MO: NoMonths or Months.
+// relief for the 168-VGPR pair kernel).  MO: NoMonths or Months.  The ET
+// kernels: PR = EvapProf (the year's evaporation sum, from zero) and
+// MO = MonthsEt; row evap is then that sum, divided like row rnf, and the day
+// snapshot carries it (SV_EVAP).  With any other PR row evap is the
+// reference's +0 and none of those statements exists.
 template <int L, class G, class SP, class CS, bool Park = true, class PR = NoProf, class MO = NoMonths>
 H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_float *forc, size_t fday,
                           size_t fvar, int nt, int nisurf, int grow_on, gbl_float *acc, size_t astride,
@@ -2525,6 +2573,7 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
       if (act && !snapped && in_column) {
         H9G_BR(BR_SNAP);
         save_day<L>(sp, cs, s, rnf_sum, ns);
+        if constexpr (kEvap<PR>) cs.sv_set_sc(SV_EVAP, pr.sum);
         snapped = true;
       }
       if constexpr (CS::kFront) {            // the substep's state to the front wave (front_year_pair)
@@ -2576,7 +2625,10 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
 #pragma unroll
     for (int k = 0; k < 12 + L; k++)
       if (later(k)) A[k * as] = a[k];
-    mo.template day_end<L>(day, nt, A, as, rnf_sum);
+    if constexpr (kEvap<PR>)
+      mo.template day_end<L>(day, nt, A, as, rnf_sum, pr.sum);
+    else
+      mo.template day_end<L>(day, nt, A, as, rnf_sum);
   }
   if constexpr (CS::kFront) front_done(cs);   // the year's end: the front wave leaves
   // :263-290
@@ -2584,11 +2636,15 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
   opaque(A);
   if (raw) {                   // the cell order's day-1 probe: the running sums themselves
     A[A_RNF * as] = rnf_sum;
+    if constexpr (kEvap<PR>) A[A_EVAP * as] = pr.sum;
     return 0;
   }
   A[A_PM * as] = A[A_PM * as] / (float)nt;
   A[A_RNF * as] = rnf_sum / (float)(nt * nisurf);
-  A[A_EVAP * as] = zero / (float)(nt * nisurf);
+  if constexpr (kEvap<PR>)
+    A[A_EVAP * as] = pr.sum / (float)(nt * nisurf);
+  else
+    A[A_EVAP * as] = zero / (float)(nt * nisurf);
 #pragma unroll
   for (int k = A_TAS; k <= A_H2O; k++) A[k * as] = A[k * as] / (float)nt;
   return 0;

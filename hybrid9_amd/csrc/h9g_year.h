@@ -2,8 +2,9 @@
 // the table of launch shapes (H9G_YEAR_SHAPES: one row per kernel, from which
 // the kernel definitions, the launch's cases and the reported names are
 // made), the kernel kinds, the geometry dispatch and launch_shape.  Included
-// by h9g.hip, which instantiates the plain kernels, and by h9g_mon.hip, which
-// instantiates the monthly ones, so that the two compile side by side
+// by h9g.hip, which instantiates the plain kernels, by h9g_mon.hip, which
+// instantiates the monthly ones, and by h9g_et.hip, which instantiates the
+// evapotranspiration (ET) ones, so that the three compile side by side
 // (hybrid9_amd/build.py); tools/isa_unit.hip instantiates single kernels for
 // the ISA study.
 #pragma once
@@ -124,7 +125,8 @@ enum Kind : int {
 
 // Launch shapes: what a year launch actually runs on, one row per year kernel.
 //   X(id, stem, kind, threads, blocks, cols, waves, pair, g2)
-// stem: the kernel is h9g_<stem>_kernel, its monthly sibling h9g_<stem>_mon_kernel;
+// stem: the kernel is h9g_<stem>_kernel, its monthly sibling h9g_<stem>_mon_kernel,
+// its ET sibling h9g_<stem>_et_kernel;
 // kind: the statistics row it counts under; threads per workgroup; column
 // blocks per workgroup; columns per wave (per column block); waves per SIMD =
 // workgroups resident per CU (the Pacer's round, pace_mode); pair: a pair
@@ -154,6 +156,7 @@ enum Shape : int { H9G_YEAR_SHAPES(H9G_SHAPE_ID) S_NSHAPE };
 
 struct ShapeInfo {
   const char *name;     // the kernel's name
+  const char *et_name;  // its ET sibling's (what an ET context's years run on)
   Kind kind;
   int threads, blocks, wave_cols, waves;
   bool pair, second_group;
@@ -163,7 +166,7 @@ struct ShapeInfo {
 constexpr ShapeInfo shape_info(Shape s) {
   switch (s) {
 #define H9G_SHAPE_ROW(id, stem, kind, threads, blocks, cols, waves, pair, g2) \
-  case id: return {"h9g_" #stem "_kernel", kind, threads, blocks, cols, waves, pair, g2};
+  case id: return {"h9g_" #stem "_kernel", "h9g_" #stem "_et_kernel", kind, threads, blocks, cols, waves, pair, g2};
     H9G_YEAR_SHAPES(H9G_SHAPE_ROW)
 #undef H9G_SHAPE_ROW
     default: return {};
@@ -216,8 +219,12 @@ inline Shape year_shape(int kind, size_t cells) {
 // FRONT: the one-column kernel's two-wave shape (h9g_pair.h front_year_pair):
 // a workgroup is one column, wave 0 its main wave and wave 1 its front wave,
 // both on the column's one LDS block.
-template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT = false>
+// ET: the evapotranspiration kernels (cell_year_pair with EvapProf and
+// MonthsEt: row evap of the annual and monthly rows is the year's evaporation
+// sum); `mon` may be null there (no monthly recording), a wave-uniform test.
+template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT = false, bool ET = false>
 __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr) {
+  static_assert(!(MON && ET), "the ET kernels record months themselves");
   typedef PairStore<L, 2 * C, R, FRONT ? 1 : 0> PS;
   static_assert(!FRONT || C == 1, "the front wave serves a one-column wave");
   constexpr int NW = FRONT ? 1 : H9G_PWAVES;               // column blocks per workgroup
@@ -307,6 +314,8 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
       if (h == 0 && !front_wave) nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);
       if constexpr (MON)
         if (h == 0 && !front_wave) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
+      if constexpr (ET)
+        if (mon && h == 0 && !front_wave) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
       return;
     }
     cell_inv_pair<L, G>(g, cs);
@@ -336,7 +345,12 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
     for (int k = 0; k < 8; k++) a.stamps[(blockIdx.x * NW + wave) * 8 + k] = pr.acc[k];
 #else
   int code;
-  if constexpr (MON)
+  if constexpr (ET)
+    code = cell_year_pair<L, G, Split2, PS, true, EvapProf, MonthsEt>(
+        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf, a.grow_on,
+        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, EvapProf{zero, g.dt()},
+        MonthsEt{mon ? (gbl_float *)(mon + io) : nullptr, ios});
+  else if constexpr (MON)
     code = cell_year_pair<L, G, Split2, PS, true, NoProf, Months>(
         g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf, a.grow_on,
         (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, NoProf(), Months{(gbl_float *)(mon + io), ios});
@@ -355,6 +369,8 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
     stop_write(err, n, cw, code, eday, estep, errval, a.err_flag);
     nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);
     if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);
+    if constexpr (ET)
+      if (mon) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);
   }
 }
 
@@ -364,6 +380,9 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
 // argument after KArgs -- KArgs itself is the same, so the plain kernels keep
 // their argument layout and their machine code.  The monthly kernels are
 // launched only by a context with monthly recording on, never by a probe.
+// And each with its ET sibling (h9g_set_evap), the same way: EvapProf and
+// MonthsEt, `mon` null without monthly recording.  An ET context runs every
+// year launch on them, its day-1 probes included.
 //   * pair2: the pair kernel built for 2 waves per SIMD (round 4, VERDICT r03
 //     #2/#4): 256 VGPRs, so the L = 10 substep does not spill (the 3-wave build
 //     spills 108 VGPRs and 118 SGPRs into a 296-B-per-lane scratch that reaches
@@ -402,6 +421,11 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
   template <int L, class G>                                                                                      \
   __global__ void H9G_YEAR_ATTRS(id) h9g_##stem##_mon_kernel(const KArgs a, float *mon, const G g) {             \
     pair_body<L, G, shape_info(id).waves, shape_info(id).wave_cols, true, shape_info(id).front()>(a, g, mon);    \
+  }                                                                                                              \
+  template <int L, class G>                                                                                      \
+  __global__ void H9G_YEAR_ATTRS(id) h9g_##stem##_et_kernel(const KArgs a, float *mon, const G g) {              \
+    pair_body<L, G, shape_info(id).waves, shape_info(id).wave_cols, false, shape_info(id).front(), true>(a, g,   \
+                                                                                                        mon);   \
   }
 H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
 #undef H9G_PAIR_KERNELS
@@ -412,9 +436,10 @@ H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
 // The body is a macro, expanded in place in the kernel and in its monthly
 // sibling (MON, `mon`: pair_body's): as an inlined function the same
 // statements compiled to other machine code for the kernel (blockDim.x loaded
-// from the dispatch packet; as with the row macros of h9g_rows.h).
-#define H9G_SOLO_BODY(MON, mon)                                                                                    \
-  typedef SoloStore<L> SS;                                                                                         \
+// from the dispatch packet; as with the row macros of h9g_rows.h).  ET: the
+// ET sibling (pair_body's; its store has the snapshot field SV_EVAP).
+#define H9G_SOLO_BODY(MON, ET, mon)                                                                                \
+  typedef SoloStore<L, ET> SS;                                                                                     \
   __shared__ uint64_t s_e2[32];                                                                                    \
   __shared__ double s_l2[32];                                                                                      \
   __shared__ float s_cell[SS::ROWS * H9G_YBLOCK];                                                                  \
@@ -438,13 +463,20 @@ H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
   if (!(ts_sum > SOIL_TRUNC) || a.err[c] != 0) {                                                                   \
     nan_rows(a.annual, Rows<L>::ANNUAL, ios, io);                                                                  \
     if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);                                      \
+    if constexpr (ET)                                                                                              \
+      if (mon) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);                                              \
     return;                                                                                                        \
   }                                                                                                                \
   cell_inv_pair<L, G>(g, cs);                                                                                      \
   int eday = 0, estep = 0;                                                                                         \
   float errval = 0.0f;                                                                                             \
   int code;                                                                                                        \
-  if constexpr (MON)                                                                                               \
+  if constexpr (ET)                                                                                                \
+    code = cell_year_pair<L, G, SplitAll, SS, false, EvapProf, MonthsEt>(                                          \
+        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, a.nt, a.nisurf, a.grow_on,                    \
+        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, EvapProf{zero, g.dt()},                  \
+        MonthsEt{mon ? (gbl_float *)(mon + io) : nullptr, ios});                                                   \
+  else if constexpr (MON)                                                                                          \
     code = cell_year_pair<L, G, SplitAll, SS, false, NoProf, Months>(                                              \
         g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, a.nt, a.nisurf, a.grow_on,                    \
         (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, NoProf(),                                \
@@ -463,15 +495,21 @@ H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
     stop_write(a.err, n, cw, code, eday, estep, errval, a.err_flag);                                               \
     nan_rows(a.annual, Rows<L>::ANNUAL, ios, iow);                                                                 \
     if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);                                     \
+    if constexpr (ET)                                                                                              \
+      if (mon) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, iow);                                             \
   }
 
 template <int L, class G>
 __global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_kernel(const KArgs a, const G g) {
-  H9G_SOLO_BODY(false, ((float *)nullptr))
+  H9G_SOLO_BODY(false, false, ((float *)nullptr))
 }
 template <int L, class G>
 __global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_mon_kernel(const KArgs a, float *mon, const G g) {
-  H9G_SOLO_BODY(true, mon)
+  H9G_SOLO_BODY(true, false, mon)
+}
+template <int L, class G>
+__global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_et_kernel(const KArgs a, float *mon, const G g) {
+  H9G_SOLO_BODY(false, true, mon)
 }
 
 // ---------------------------------------------------------------------------
@@ -516,12 +554,14 @@ int geo_dispatch(const h9g_config &cfg, F &&f) {
 #endif
 }
 
-// The year kernel of `shape` -- MON: its monthly sibling, with `mon` the base
-// of the launch's monthly rows -- over a's slots [c0, cend), with the
-// configuration's geometry variant.  h9g.hip instantiates the plain case;
-// the monthly case is h9g_mon_launch of h9g_mon.hip, so each unit compiles
-// only its own kernels.
-template <bool MON>
+// The year kernel of `shape` -- V_MON: its monthly sibling, with `mon` the
+// base of the launch's monthly rows; V_ET: its ET sibling, `mon` the same or
+// null -- over a's slots [c0, cend), with the configuration's geometry
+// variant.  h9g.hip instantiates the plain case; the monthly case is
+// h9g_mon_launch of h9g_mon.hip and the ET case h9g_et_launch of h9g_et.hip,
+// so each unit compiles only its own kernels.
+enum Variant : int { V_PLAIN = 0, V_MON, V_ET };
+template <Variant V>
 int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const KArgs &a, float *mon) {
   const unsigned grid = (unsigned)shape_blocks(shape, (size_t)(a.cend - a.c0)), block = (unsigned)shape_info(shape).threads;
   return geo_dispatch(cfg, [&](auto L, auto g) {
@@ -529,7 +569,8 @@ int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const K
 #define H9G_SHAPE_CASE(id, stem, ...)                                                              \
   case id:                                                                                         \
     if constexpr (!shape_at(id, L)) return (int)H9G_EINVAL;                                        \
-    else if constexpr (MON) h9g_##stem##_mon_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, mon, g); \
+    else if constexpr (V == V_ET) h9g_##stem##_et_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, mon, g); \
+    else if constexpr (V == V_MON) h9g_##stem##_mon_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, mon, g); \
     else h9g_##stem##_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, g);                    \
     return 0;
       H9G_YEAR_SHAPES(H9G_SHAPE_CASE)
@@ -539,7 +580,8 @@ int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const K
   });
 }
 
-// h9g_mon.hip: launch_shape<true>, and the cell order's NaN rows of the cells
-// that start a decade stopped.
+// h9g_mon.hip: launch_shape<V_MON>, and the cell order's NaN rows of the cells
+// that start a decade stopped.  h9g_et.hip: launch_shape<V_ET>.
 int h9g_mon_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
+int h9g_et_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
 int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);

@@ -368,6 +368,26 @@ INTERFACE
     INTEGER(C_INT64_T), INTENT(IN) :: gid (*)
     INTEGER(C_INT) :: h9g_write_mxy_nc
   END FUNCTION
+  ! The same file from the snapshots of an ET run (h9g_set_evap): evaporation
+  ! divided by days_m * nisurf, like runoff.
+  FUNCTION h9g_write_mxy_nc_evap (path, nx, ny, nlayers, zc, ncell, gid, jyear, nisurf, snapshots) &
+      BIND(C, NAME='h9g_write_mxy_nc_evap')
+    IMPORT :: C_INT, C_CHAR, C_FLOAT, C_INT64_T
+    CHARACTER(KIND=C_CHAR), INTENT(IN) :: path (*)
+    INTEGER(C_INT), VALUE :: nx, ny, nlayers, ncell, jyear, nisurf
+    REAL(C_FLOAT), INTENT(IN) :: zc (*), snapshots (*)
+    INTEGER(C_INT64_T), INTENT(IN) :: gid (*)
+    INTEGER(C_INT) :: h9g_write_mxy_nc_evap
+  END FUNCTION
+  ! Evapotranspiration output: on /= 0 makes later runs use the ET year
+  ! kernels, whose row evap of the annual means and of the month-end snapshots
+  ! is the year's evaporation sum; 0 (default): the reference's zero.
+  FUNCTION h9g_set_evap (ctx, on) BIND(C, NAME='h9g_set_evap')
+    IMPORT :: C_PTR, C_INT
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: on
+    INTEGER(C_INT) :: h9g_set_evap
+  END FUNCTION
   FUNCTION h9g_last_kernel_ms (ctx) BIND(C, NAME='h9g_last_kernel_ms')
     IMPORT :: C_PTR, C_FLOAT
     TYPE(C_PTR), VALUE :: ctx

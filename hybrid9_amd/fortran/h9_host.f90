@@ -50,6 +50,11 @@ PROGRAM H9_HOST
 ! given (the decades stay overlapped).  On a grid the cells sit at their grid
 ! ids; a case's cells form a grid of one row, in their order.
 !
+! evap = 1 turns evapotranspiration recording on (h9g_set_evap, DESIGN.md §7):
+! the evaporation field of axyYYYY.nc, of annual.f32 and, with monthly = 1, of
+! mxyYYYY.nc (then written by h9g_write_mxy_nc_evap) is the year's evaporation
+! sum instead of the reference's zero, in both cell_order settings.
+!
 ! Usage:  h9_host [driver.txt] [h9gpu.nml]
 ! Outputs: <out_dir>/annual.f32 (ncell, 12+L, nyears),
 !          <out_dir>/state_end.f32 (packed state, include/h9g.h) and, on a
@@ -70,11 +75,11 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 ! --- extension namelist ----------------------------------------------------
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
-INTEGER :: cell_order, ordered_decades, daily, monthly
+INTEGER :: cell_order, ordered_decades, daily, monthly, evap
 INTEGER(C_INT64_T) :: seed
 NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
-                 cell_order, ordered_decades, daily, monthly
+                 cell_order, ordered_decades, daily, monthly, evap
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
 TYPE(C_PTR) :: pgf_ptr (7)
 CHARACTER (LEN = *), PARAMETER :: pgf_var (7) = &
@@ -119,7 +124,7 @@ INTEGER :: mnx, mny
 input_mode = 'synth'; case_dir = ''; out_dir = '.'; pgf_dir = '.'
 nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
-monthly = 0
+monthly = 0; evap = 0
 daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
 PATH_output = '.'
 seed = 20161123_C_INT64_T
@@ -311,6 +316,7 @@ IF (daily /= 0) THEN
                   &  theta_ma_1,  lai,  lai_litter, w_i, fT'
   END IF
 END IF
+IF (evap /= 0) CALL chk (h9g_set_evap (ctx, 1))
 IF (monthly /= 0) THEN
   CALL chk (h9g_set_monthly (ctx, 1))
   ALLOCATE (mon (ncell, 12 + L, H9G_NMONTHS), mgid (ncell))
@@ -427,8 +433,13 @@ CONTAINS
     INTEGER, INTENT(IN) :: k, y
     CALL chk (h9g_get_monthly (ctx, k, mon))
     WRITE (ydate,'(I4)') y
-    CALL chk (h9g_write_mxy_nc (TRIM (out_dir)//'/mxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, L, zc, ncell, &
-                                mgid, y, NISURF, mon))
+    IF (evap /= 0) THEN
+      CALL chk (h9g_write_mxy_nc_evap (TRIM (out_dir)//'/mxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, L, zc, &
+                                       ncell, mgid, y, NISURF, mon))
+    ELSE
+      CALL chk (h9g_write_mxy_nc (TRIM (out_dir)//'/mxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, L, zc, ncell, &
+                                  mgid, y, NISURF, mon))
+    END IF
   END SUBROUTINE month_out
 
   ! The daily lines of year k (0-based) of the last run, calendar year y,

@@ -287,6 +287,31 @@ int h9g_set_monthly(h9g_ctx *ctx, int on);
  * H9G_EINVAL for a bad k. */
 int h9g_get_monthly(h9g_ctx *ctx, int k, float *out);
 
+/* --- evapotranspiration output: the ET year kernels ---------------------- */
+/* The reference sets evap_sum = 0 at the start of a year (HYBRID9.f90:137)
+ * and never adds to it, so row evap of the annual means and of every
+ * snapshot is +0.  With ET recording on, every year launch of the context
+ * (the cell order's day-1 probes included) runs the ET year kernels, the
+ * year kernels under other names, which accumulate, in f32 with no
+ * contraction,
+ *   evap_sum = evap_sum + (qflx_evap_grnd + qflx_tran_veg_col) * dt
+ * after every substep -- the expression of :207-208's evap_day in the form
+ * of rnf_sum's HYDROLOGY.f90:1282-1283, qflx_evap_grnd after the
+ * MIN(em1, .) of :396-400, dt = 86400 / NISURF -- and survive the exact
+ * re-run.  Row evap of h9g_get_annual is then evap_sum / FLOAT(nt * NISURF)
+ * as :276 is written: the convention of row rnf (the sum is in mm, the mean
+ * mm per substep; the file attribute "mm/s" is the reference's label and
+ * stays).  Row evap of a month-end snapshot is evap_sum as it stands, like
+ * rnf_sum.  Only the total is recorded: the ground/canopy partition stays
+ * with the daily line.  Every other annual and monthly row, the state, the
+ * STOP records and the daily lines are the same bits with recording on or
+ * off; a cell that stops has NaN in row evap like in every other.  With
+ * recording off (the default) nothing changes: no launch, allocation or
+ * synchronisation is added, and row evap is the reference's +0.  No buffer
+ * of its own (h9g_config_bytes is unchanged).  H9G_EINVAL for a null
+ * context.  h9g_kernel_name then reports the ET kernel. */
+int h9g_set_evap(h9g_ctx *ctx, int on);
+
 /* --- outputs (HYBRID9.f90:263-290) ------------------------------------ */
 /* Annual means of the last year run, (12+L) rows of (ncell):
  * npp plant_mass rnf evap tas rlds rsds huss ps pr rhs theta(1..L)
@@ -332,6 +357,11 @@ int h9g_write_axy_nc(const char *path, int nx, int ny, int nlayers,
 int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers,
                      const float *zc, int ncell, const int64_t *gid, int jyear,
                      int nisurf, const float *snapshots);
+/* The same file from the snapshots of an ET run (h9g_set_evap): row
+ * evaporation is divided by days_m * nisurf, like runoff. */
+int h9g_write_mxy_nc_evap(const char *path, int nx, int ny, int nlayers,
+                          const float *zc, int ncell, const int64_t *gid,
+                          int jyear, int nisurf, const float *snapshots);
 /* READ_PGF.f90 / READ_NET_CDF_3DR.f90: days [t0, t0+nt) of variable 4
  * (time, lat, lon) of the 7 PGF files (tas rlds rsds huss ps pr rhs)
  * gathered at the grid ids gid into out (7, nt, ncell).  Host only. */

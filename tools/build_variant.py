@@ -19,7 +19,7 @@ def main() -> None:
         extra = [e for e in extra if e != "--c2"] + ["-DH9G_ONLY_C2"]
     out = hb.OUT.with_name(f"libh9g_{tag}.so")
     cmd = [hb.hipcc(), f"--offload-arch={hb.ARCH}", *hb.FLAGS, *extra, hb.id_flag(extra), str(hb.SRC),
-           str(hb.SRC_MON), str(hb.SRC_IO), "-o", str(out)]
+           str(hb.SRC_MON), str(hb.SRC_ET), str(hb.SRC_IO), "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.exit(f"{tag}: hipcc failed\n{r.stderr[-3000:]}")
