@@ -8,6 +8,7 @@ Needs /root/reference (build container only); the fixtures are data and
 travel with the repo.
 
     python tests/golden/make_golden.py            # all cases
+    python tests/golden/make_golden.py main_geo   # one group (any main_* below)
 
 Each npz holds: meta (json string), annual (nyears, 12+L, ncell),
 state (packed, refcase.state_fields), optionally trace (ntrace, nsteps, 3L+7)
@@ -65,16 +66,25 @@ def save(name, meta, out, extra=None):
           f"{(OUT / f'{name}.npz').stat().st_size / 1e3:.0f} kB")
 
 
-def synth_case(name, gid, *, year0=1901, nyears=1, nisurf=48, grow_on=1, trace=()):
+def synth_case(name, gid, *, year0=1901, nyears=1, nisurf=48, grow_on=1, trace=(), zi=None, kind="synth",
+               check=None):
+    """zi: the layer interfaces zi(0:L+1) in mm (default: driver.txt's L = 8
+    layers); L = 10 takes the 0.25 deg inputs (l10_inputs) and h9ref_l10.
+    check(out, zi): conditions on the reference's output (raises)."""
     gid = np.asarray(gid, dtype=np.int64)
-    p, f = synth_inputs(gid, year0, nyears)
-    out = refcase.run_case(zi=synth.ZI_L8, params=p, forcing=f, nisurf=nisurf, year0=year0,
+    zi = synth.ZI_L8 if zi is None else np.asarray(zi, np.float32)
+    L = zi.size - 2
+    p, f = synth_inputs(gid, year0, nyears) if L == 8 else l10_inputs(gid, year0, nyears)
+    out = refcase.run_case(zi=zi, params=p, forcing=f, nisurf=nisurf, year0=year0,
                            nyears=nyears, grow_on=grow_on, trace_cells=trace)
-    meta = dict(name=name, kind="synth", seed=synth.SEED, gid=gid.tolist(), L=8,
+    if check is not None:
+        check(out, zi)
+    meta = dict(name=name, kind=kind, seed=synth.SEED, gid=gid.tolist(), L=L,
                 ncell=int(gid.size), year0=year0, nyears=nyears, nisurf=nisurf,
-                grow_on=grow_on, zi=synth.ZI_L8.tolist(), trace_cells=list(trace),
+                grow_on=grow_on, zi=zi.tolist(), grid="05" if L == 8 else "025", trace_cells=list(trace),
                 input_sha256=digest(packed_params(p), f),
-                generator="oracle/_ref/h9ref (reference HYDROLOGY.f90/GROW.f90, amdflang -O2)")
+                generator=f"oracle/_ref/{refcase.ref_bin(L).name} (reference HYDROLOGY.f90/GROW.f90"
+                          f"{'' if L == 8 else ' with nsoil_layers_max=10, Nlevgrnd=11'}, amdflang -O2)")
     save(name, meta, out)
 
 
@@ -95,21 +105,26 @@ def independent_layer_params(gid, L=8, seed=synth.SEED):
                 fmax=(F32(0.1) + F32(0.5) * u(synth.S_FMAX, gid)).astype(F32))
 
 
-def stop_case(name, gid, *, year0=1901, nisurf=24, grow_on=1):
+def stop_case(name, gid, *, year0=1901, nisurf=24, grow_on=1, zi=None):
     """Explicit inputs on which the reference executes a STOP: the fixture
     is the STOP site and the values the reference prints."""
     gid = np.asarray(gid, dtype=np.int64)
+    zi = synth.ZI_L8 if zi is None else np.asarray(zi, np.float32)
     p = independent_layer_params(gid)
     f = synth.make_forcing(gid, synth.cell_lat(gid), synth.year_day0(year0), 365)
     try:
-        refcase.run_case(zi=synth.ZI_L8, params=p, forcing=f, nisurf=nisurf, year0=year0,
+        refcase.run_case(zi=zi, params=p, forcing=f, nisurf=nisurf, year0=year0,
                          nyears=1, grow_on=grow_on)
     except refcase.RefStop as e:
         info = e.info
     else:
         raise SystemExit(f"{name}: expected a reference STOP")
+    # the reference prints its REAL*4 with the fewest digits that read back as
+    # the same float32 (8 or 9): `value` is that float32, exactly, so that it
+    # formats like any other float32; `value_printed` is the text's number
+    info = dict(info, value=float(np.float32(info["value"])), value_printed=info["value"])
     meta = dict(name=name, kind="stop", L=8, ncell=int(gid.size), year0=year0, nyears=1,
-                nisurf=nisurf, grow_on=grow_on, zi=synth.ZI_L8.tolist(), stop=info,
+                nisurf=nisurf, grow_on=grow_on, zi=zi.tolist(), stop=info,
                 generator="oracle/_ref/h9ref STOP output")
     np.savez_compressed(OUT / f"{name}.npz", meta=np.array(json.dumps(meta)),
                         params=packed_params(p), forcing=f)
@@ -343,17 +358,21 @@ def rel_bound(a, b):
     return float(r.max()) if r.size else 0.0
 
 
-def cell_order_case(name, gid, *, year0=1901, nyears=30, nisurf=48, grow_on=1, split=None, L=8):
+def cell_order_case(name, gid, *, year0=1901, nyears=30, nisurf=48, grow_on=1, split=None, L=8, zi=None,
+                    min_carried=0):
     """The reference as it really runs: h9ref's cell_order
     mode, decade -> cell -> year with smp carried from cell to cell
     (HYBRID9.f90:93-130, HYDROLOGY.f90:270-275, SHARED.f90:198), cells in
     the reference's (y, x) order.  Also records, as data, how far the
     isolated-cell contract (every cell its own smp) sits from it, and
     (split) how far the reference itself moves when its cells are cut into
-    two ranks (two chains, INIT.f90:271-274)."""
+    two ranks (two chains, INIT.f90:271-274).  zi: the layer interfaces
+    (default: the L = 8 / L = 10 defaults).  min_carried: the least number
+    of cell-years in which the carry must change a bit of the annual means."""
     gid = np.asarray(gid, dtype=np.int64)
     p, f = synth_inputs(gid, year0, nyears) if L == 8 else l10_inputs(gid, year0, nyears)
-    zi = synth.ZI_L8 if L == 8 else synth.ZI_L10
+    zi = (synth.ZI_L8 if L == 8 else synth.ZI_L10) if zi is None else np.asarray(zi, np.float32)
+    assert zi.size == L + 2
     kw = dict(zi=zi, params=p, forcing=f, nisurf=nisurf, year0=year0, nyears=nyears,
               grow_on=grow_on)
     co = refcase.run_case(cell_order=True, **kw)
@@ -362,12 +381,15 @@ def cell_order_case(name, gid, *, year0=1901, nyears=30, nisurf=48, grow_on=1, s
     fields = refcase.annual_fields(L)
     pick = [fields.index(k) for k in ["rnf", "theta_total"] + [f"theta{i + 1}" for i in range(L)]]
     diff_cells = np.any(np.any(ai.view(np.uint32) != ac.view(np.uint32), axis=0), axis=0)
+    carried = int(np.any(ai.view(np.uint32) != ac.view(np.uint32), axis=1).sum())
+    if carried < min_carried:
+        raise SystemExit(f"{name}: the carry changes {carried} cell-years, fewer than {min_carried}")
     first_year = [int(year0 + np.argmax(np.any(ai[:, :, c].view(np.uint32) != ac[:, :, c].view(np.uint32), axis=1)))
                   for c in np.where(diff_cells)[0]]
     iso_bound = dict(
         annual=rel_bound(ai[:, pick, :], ac[:, pick, :]),
         **{k: rel_bound(iso["state"][k], co["state"][k]) for k in ("h2osoi_liq", "zwt", "wa")},
-        cells_differing=int(diff_cells.sum()),
+        cells_differing=int(diff_cells.sum()), cell_years_differing=carried,
         first_decade_bitwise=bool(np.array_equal(ai[:min(nyears, 10)].view(np.uint32),
                                                  ac[:min(nyears, 10)].view(np.uint32))),
         first_year_hist={str(y): first_year.count(y) for y in sorted(set(first_year))})
@@ -555,6 +577,54 @@ def main_lclim():
                events=LCLIM_EVENTS_2004, stop=True, soils="independent", ppt_scale=10.0)
 
 
+# Layer sets (mm) other than the two the kernels hold at compile time
+# (synth.ZI_L8 = driver.txt's, synth.ZI_L10 = config 5's): A and C with integer
+# interfaces, B with none, so that dz/2, the node depths and the node spacings
+# all round.
+ZI_GEO_A = np.array([0, 30, 80, 150, 260, 430, 700, 1100, 1700, 4400], np.float32)
+ZI_GEO_B = np.array([0, 17.5, 50.3, 120.7, 250.1, 500.9, 900.3, 1500.7, 2600.1, 5300.9], np.float32)
+ZI_GEO_C = np.array([0, 10, 30, 70, 130, 220, 380, 640, 1050, 1700, 2700, 4200], np.float32)
+
+
+def geo_check(name):
+    """Conditions on a `geo` case's reference output: no NaN, and the water
+    table ends inside the column (zwt * 1000 < zi(L)) for at least 4 cells
+    and below it for at least 4 (the one-column kernel's task lanes take
+    different work in the two regimes)."""
+    def check(out, zi):
+        L = zi.size - 2
+        if np.isnan(out["annual"]).any() or np.isnan(refcase.pack_state(out["state"], L)).any():
+            raise SystemExit(f"{name}: NaN in the reference's output")
+        inside = int(((out["state"]["zwt"] * np.float32(1000.0)) < zi[L]).sum())
+        below = int(out["state"]["zwt"].size) - inside
+        print(f"{name}: water table inside the column in {inside} cells, below it in {below}")
+        if inside < 4 or below < 4:
+            raise SystemExit(f"{name}: water table inside/below the column {inside}/{below}: need 4 of each")
+    return check
+
+
+def main_geo():
+    """Runtime layer geometry (the GeoR instantiations of the year kernels)
+    pinned to the reference: three isolated-cell cases of kind `geo` (their
+    own kind, so that no test parametrised over synth/explicit/spinup picks
+    them up), the reference's own cell order at layers A, and a STOP at
+    layers A."""
+    land = synth.land_cells()
+    g32 = land[7::389][:32]
+    synth_case("geo_a_ns36", g32, year0=1903, nyears=2, nisurf=36, grow_on=1, zi=ZI_GEO_A, kind="geo",
+               check=geo_check("geo_a_ns36"))
+    synth_case("geo_b_ns12", g32, year0=1903, nyears=2, nisurf=12, grow_on=0, zi=ZI_GEO_B, kind="geo",
+               check=geo_check("geo_b_ns12"))
+    l4 = synth.land_cells(synth.NX025, synth.NY025, synth.NLAND025)
+    synth_case("geo_c_ns24", l4[11::1601][:32], year0=1903, nyears=2, nisurf=24, grow_on=1, zi=ZI_GEO_C, kind="geo",
+               check=geo_check("geo_c_ns24"))
+    g10 = np.array([(80 + j) * synth.NX05 + 400 + i for j in range(10) for i in range(10)])
+    cell_order_case("co_geo_a", g10[:40], nyears=20, nisurf=36, zi=ZI_GEO_A, min_carried=20)
+    stop_case("stop_geo_ns36", land[263::527][90:98], nisurf=36, zi=ZI_GEO_A)
+    for n in ("geo_a_ns36", "geo_b_ns12", "geo_c_ns24", "co_geo_a", "stop_geo_ns36"):
+        assert (OUT / f"{n}.npz").stat().st_size < (OUT / "co_c1_30yr.npz").stat().st_size, n
+
+
 def main():
     if not refcase.REF_BIN.exists():
         sys.exit("build the reference harness first: make -C oracle ref")
@@ -576,6 +646,7 @@ def main():
     l10_case()
     bench_stop_case()
     main_cell_order()
+    main_geo()
 
 
 if __name__ == "__main__":
