@@ -9,21 +9,50 @@ f32 division/sqrt and f32 denormal support are kept (no fast-math).
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
-SRC = HERE / "csrc" / "h9g.hip"
-SRC_MON = HERE / "csrc" / "h9g_mon.hip"     # the monthly kernels: h9g_year.h's kernels with the Months policy
-SRC_ET = HERE / "csrc" / "h9g_et.hip"       # the ET kernels: the same kernels with the EvapProf and MonthsEt policies
-SRC_IO = HERE / "csrc" / "h9g_io.cpp"       # host-only NetCDF I/O
-DEPS = [SRC, SRC_MON, SRC_ET, SRC_IO, HERE / "csrc" / "h9g_year.h", HERE / "csrc" / "h9_math.h", HERE / "csrc" / "h9g_step.h",
-        HERE / "csrc" / "h9g_synth.h", HERE / "csrc" / "h9g_geo.h",
-        HERE / "csrc" / "h9g_pair.h", HERE / "csrc" / "h9g_expr.h", HERE / "csrc" / "h9g_rows.h",
-        HERE / "csrc" / "h9g_io.h",
-        HERE.parent / "include" / "h9g.h"]
+CSRC = HERE / "csrc"
+# The translation units and the flags each gets beyond FLAGS.  ID: the build-id
+# flag, for the unit that defines h9g_build_id alone (a digest of every unit:
+# with it a unit is recompiled whenever any other changes).
+ID = object()
+UNITS = [
+    (CSRC / "h9g.hip", []),         # host runtime: context, forcing, the year launch, recording; its small kernels
+    (CSRC / "h9g_ord.hip", []),     # host runtime: the ordered mode and its small kernels
+    (CSRC / "h9g_aux.hip", []),     # soil build, synthetic inputs, self-tests
+    (CSRC / "h9g_plain.hip", []),   # the plain year kernels (h9g_year.h)
+    (CSRC / "h9g_mon.hip", []),     # the monthly kernels: the same kernels with the Months policy
+    (CSRC / "h9g_et.hip", []),      # the ET kernels: the same kernels with the EvapProf and MonthsEt policies
+    (CSRC / "h9g_cols.hip", []),    # the other geometry-templated kernels: init, sort, site, focus
+    (CSRC / "h9g_io.cpp", [ID]),    # host-only NetCDF I/O, and h9g_build_id
+]
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+def unit_deps(src: Path) -> list[Path]:
+    """A unit and the headers it reaches through quoted #includes, transitively
+    (whatever an #if around them says): what its object is compiled from."""
+    seen, todo = [], [src]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.append(f)
+        todo += [(f.parent / m).resolve() for m in _INCLUDE.findall(f.read_text())]
+    return [seen[0], *sorted(seen[1:])]
+
+
+def deps() -> list[Path]:
+    """Every file the library is compiled from: the units in UNITS' order, then their headers."""
+    per = [unit_deps(src) for src, _ in UNITS]
+    return [u[0] for u in per] + sorted({h for u in per for h in u[1:]})
+
+
 OUT = HERE / "lib" / "libh9g.so"
 ARCH = os.environ.get("H9G_ARCH", "gfx950")
 
@@ -46,7 +75,7 @@ def build_id(extra=()) -> str:
     attaches counters only to the build they were measured on."""
     import hashlib
     hs = hashlib.sha256()
-    for d in DEPS:
+    for d in deps():
         hs.update(d.name.encode() + b"\0" + d.read_bytes() + b"\0")
     hs.update(" ".join([ARCH, *FLAGS, *extra]).encode())
     return hs.hexdigest()[:16]
@@ -60,7 +89,7 @@ def up_to_date() -> bool:
     if not OUT.exists():
         return False
     t = OUT.stat().st_mtime
-    return all(d.stat().st_mtime <= t for d in DEPS)
+    return all(d.stat().st_mtime <= t for d in deps())
 
 
 def _run(cmd, verbose):
@@ -72,12 +101,11 @@ def _run(cmd, verbose):
 
 
 def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
-    """Compiles the four translation units to objects (h9g.hip with the year
-    kernels and everything else on the device, h9g_mon.hip with the monthly
-    kernels and h9g_et.hip with the ET kernels, ~4 minutes each and side by
-    side: all three include h9g_year.h; and the host-only NetCDF I/O, seconds,
-    so four compilers at the most; each only when its own
-    inputs changed, keyed by their digest) and links libh9g.so."""
+    """Compiles the translation units of UNITS to objects, side by side, each
+    only when its own inputs changed (keyed by the digest of its flags, its
+    source and the headers it includes), and links libh9g.so.  The three units
+    of year kernels take minutes each and h9g_cols.hip about one; the host
+    runtime's units and the I/O take seconds, so a change there is a short build."""
     if not force and up_to_date():
         return OUT
     OUT.parent.mkdir(parents=True, exist_ok=True)
@@ -86,25 +114,22 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
     import hashlib
     flags = [f"--offload-arch={ARCH}", *FLAGS, *extra]
     objs, jobs = [], []
-    hdrs = [d for d in DEPS if d not in (SRC, SRC_IO, SRC_MON, SRC_ET)]
-    # h9g_build_id lives in the I/O unit: only it gets the digest flag
-    for src, deps, idf in ((SRC, [SRC, *hdrs], []), (SRC_MON, [SRC_MON, *hdrs], []),
-                           (SRC_ET, [SRC_ET, *hdrs], []),
-                           (SRC_IO, [SRC_IO, HERE / "csrc" / "h9g_io.h", DEPS[-1]], [id_flag(extra)])):
-        flags_u = flags + idf
+    for src, own in UNITS:
+        flags_u = flags + [id_flag(extra) if f is ID else f for f in own]
         hs = hashlib.sha256(" ".join(flags_u).encode())
-        for d in deps:
+        for d in unit_deps(src):
             hs.update(d.read_bytes())
         o = obj / f"{src.stem}_{hs.hexdigest()[:16]}.o"
         if force or not o.exists():
-            for old in obj.glob(f"{src.stem}_*.o"):
+            # this unit's stale objects (the digest is what follows the stem: "h9g_*" would be every unit's)
+            for old in obj.glob(f"{src.stem}_{'[0-9a-f]' * 16}.o"):
                 old.unlink()
             tmp = o.with_suffix(".o.tmp")
             jobs.append(([hipcc(), *[f for f in flags_u if f != "-shared"], "-c", str(src), "-o", str(tmp)], tmp, o))
         objs.append(str(o))
     if jobs:
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(len(jobs)) as ex:
+        with ThreadPoolExecutor(min(len(jobs), 16)) as ex:
             for _ in ex.map(lambda j: (_run(j[0], verbose), os.replace(j[1], j[2])), jobs):
                 pass
     tmp = OUT.with_suffix(".so.tmp")

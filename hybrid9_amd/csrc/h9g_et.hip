@@ -1,7 +1,7 @@
 // h9g_et.hip -- the evapotranspiration (ET) kernels' translation unit: the
 // year kernels of h9g_year.h instantiated with the EvapProf and MonthsEt
 // policies (h9g_pair.h) under the ET kernels' names, behind h9g_et_launch.
-// A unit of its own so that it compiles beside h9g.hip and h9g_mon.hip
+// A unit of its own so that it compiles beside h9g_plain.hip and h9g_mon.hip
 // (hybrid9_amd/build.py), not after them.
 #include "h9g_year.h"
 

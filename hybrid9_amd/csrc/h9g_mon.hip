@@ -1,7 +1,7 @@
 // h9g_mon.hip -- the monthly kernels' translation unit: the year kernels of
 // h9g_year.h instantiated with the Months policy (h9g_pair.h) under the
 // monthly kernels' names, behind h9g_mon_launch.  A unit of its own so that it
-// compiles beside h9g.hip (hybrid9_amd/build.py), not after it.
+// compiles beside h9g_plain.hip (hybrid9_amd/build.py), not after it.
 #include "h9g_year.h"
 
 // The cell order: the cells that start a decade stopped (err0) run none

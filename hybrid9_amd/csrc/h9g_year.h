@@ -2,11 +2,13 @@
 // the table of launch shapes (H9G_YEAR_SHAPES: one row per kernel, from which
 // the kernel definitions, the launch's cases and the reported names are
 // made), the kernel kinds, the geometry dispatch and launch_shape.  Included
-// by h9g.hip, which instantiates the plain kernels, by h9g_mon.hip, which
-// instantiates the monthly ones, and by h9g_et.hip, which instantiates the
-// evapotranspiration (ET) ones, so that the three compile side by side
-// (hybrid9_amd/build.py); tools/isa_unit.hip instantiates single kernels for
-// the ISA study.
+// by h9g_plain.hip, which instantiates the plain kernels, by h9g_mon.hip,
+// which instantiates the monthly ones, and by h9g_et.hip, which instantiates
+// the evapotranspiration (ET) ones, so that the three compile side by side
+// (hybrid9_amd/build.py), beside h9g_cols.hip with the other
+// geometry-templated kernels; tools/isa_unit.hip instantiates single kernels
+// for the ISA study.  At its end: the kernel units' launchers, which is all
+// the host runtime's units (h9g_ctx.h) see of them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -557,9 +559,9 @@ int geo_dispatch(const h9g_config &cfg, F &&f) {
 // The year kernel of `shape` -- V_MON: its monthly sibling, with `mon` the
 // base of the launch's monthly rows; V_ET: its ET sibling, `mon` the same or
 // null -- over a's slots [c0, cend), with the configuration's geometry
-// variant.  h9g.hip instantiates the plain case; the monthly case is
-// h9g_mon_launch of h9g_mon.hip and the ET case h9g_et_launch of h9g_et.hip,
-// so each unit compiles only its own kernels.
+// variant.  The plain case is h9g_plain_launch of h9g_plain.hip, the monthly
+// case h9g_mon_launch of h9g_mon.hip and the ET case h9g_et_launch of
+// h9g_et.hip, so each unit compiles only its own kernels.
 enum Variant : int { V_PLAIN = 0, V_MON, V_ET };
 template <Variant V>
 int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const KArgs &a, float *mon) {
@@ -580,8 +582,82 @@ int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const K
   });
 }
 
-// h9g_mon.hip: launch_shape<V_MON>, and the cell order's NaN rows of the cells
-// that start a decade stopped.  h9g_et.hip: launch_shape<V_ET>.
+// ---------------------------------------------------------------------------
+// the kernel units' host side: what the host runtime (h9g_ctx.h) calls
+// ---------------------------------------------------------------------------
+// h9g_plain.hip: launch_shape<V_PLAIN>.  h9g_mon.hip: launch_shape<V_MON>, and
+// the cell order's NaN rows of the cells that start a decade stopped.
+// h9g_et.hip: launch_shape<V_ET>.
+int h9g_plain_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a);
 int h9g_mon_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
 int h9g_et_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
 int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);
+
+// Not exported from libh9g.so.
+#define H9G_LOCAL __attribute__((visibility("hidden")))
+
+#define HIPCHK(x)                                                              \
+  do {                                                                         \
+    hipError_t e_ = (x);                                                       \
+    if (e_ != hipSuccess) {                                                    \
+      fprintf(stderr, "h9g: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), \
+              __FILE__, __LINE__);                                             \
+      return H9G_EHIP;                                                         \
+    }                                                                          \
+  } while (0)
+
+// h9g_cols.hip: the one-lane-per-column kernels, each behind a launcher that
+// picks the configuration's geometry variant (geo_dispatch) and its grid.
+#define H9G_BLOCK 256   // threads per block of the per-cell helper kernels
+
+// h9g_site_kernel's arguments.  Parameters and state as the year kernels.
+struct SiteArgs {
+  int ncell, nday, nisurf;
+  const float *__restrict__ par;
+  float *__restrict__ st;
+  const float *__restrict__ sub, *__restrict__ daily, *__restrict__ lai;
+  float *__restrict__ out;
+  int *__restrict__ err;
+  int *__restrict__ err_flag;
+};
+
+// h9g_focus_kernel's arguments.
+struct FocusArgs {
+  int ncell, nsel, nyears, nisurf, grow_on;
+  size_t fvar;
+  const float *__restrict__ par;
+  const float *__restrict__ st;
+  const int *__restrict__ sel;
+  const int *__restrict__ err;     // the cells' STOP records when the run starts (rows of ncell)
+  const FocusYear *__restrict__ yrs;
+  float *__restrict__ out;
+};
+
+// h9g_init_kernel over the ncell cells: the reference's initial state from par.
+H9G_LOCAL int h9g_init_launch(const h9g_config *cfg, hipStream_t stream, int ncell, const float *par, float *st);
+// h9g_sort_kernel over slots [c0, cend) in workgroups of cpb cells, of the
+// cells `list` (null: the slots' own numbers) with state st and STOP rows err,
+// by the sort history hist over nsub substeps, into perm.
+H9G_LOCAL int h9g_sort_launch(const h9g_config *cfg, hipStream_t stream, int n, int c0, int cend, int cpb,
+                              const float *st, const int *err, const int *hist, int nsub, int *perm,
+                              const int *list);
+H9G_LOCAL int h9g_site_launch(const h9g_config *cfg, hipStream_t stream, const SiteArgs &a);
+H9G_LOCAL int h9g_focus_launch(const h9g_config *cfg, hipStream_t stream, const FocusArgs &a);
+
+// Measurement builds.  Their device globals (h9g_step.h, h9g_pair.h) exist
+// once per unit; these read and write the copies of h9g_plain.hip, the unit
+// whose kernels the measurement builds run (tools/build_variant.py).  The
+// monthly and ET kernels count into their own units' copies, as before the
+// plain kernels had a unit of their own; so do now h9g_site_kernel and
+// h9g_focus_kernel (h9g_cols.hip), whose substeps pass the same H9G_BR sites
+// and once shared the plain kernels' copy.  No copy but h9g_plain.hip's is
+// read or cleared: a count covers the plain year kernels alone.
+#if defined(H9G_COUNT_EXACT)
+H9G_LOCAL int h9g_exact_report(void);    // prints the exact re-run counts
+#endif
+#if defined(H9G_COUNT_BRANCH)
+H9G_LOCAL int h9g_branch_report(void);   // prints the branch counts since the last call, and clears them
+#endif
+#if defined(H9G_DUMP_AQ)
+H9G_LOCAL int h9g_aq_set(unsigned *bits, const float *base, hipStream_t stream);   // h9g_aq_bits, h9g_aq_base
+#endif

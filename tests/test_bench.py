@@ -318,6 +318,68 @@ def test_build_id_is_the_source_digest():
     assert hb.build_id(["-DX"]) != bid
 
 
+def test_build_id_covers_every_source(tmp_path, monkeypatch):
+    """Every .hip and .cpp under hybrid9_amd/csrc is a unit of build.UNITS;
+    every header there, and include/h9g.h, is reached from some unit's
+    #includes and so covered by build_id(); and a byte appended to a copy of
+    any one of them changes the id."""
+    import shutil
+    from hybrid9_amd import build as hb
+    csrc = hb.CSRC
+    units = [src for src, _ in hb.UNITS]
+    assert sorted(units) == sorted([*csrc.glob("*.hip"), *csrc.glob("*.cpp")])
+    files = sorted([*csrc.iterdir(), hb.HERE.parent / "include" / "h9g.h"])
+    assert all(f.suffix in (".hip", ".cpp", ".h") for f in files)
+    assert sorted(hb.deps()) == files
+    # the same tree layout, so that "../../include/h9g.h" resolves inside the copy
+    root = tmp_path.resolve()
+    ccopy = root / "hybrid9_amd" / "csrc"
+    shutil.copytree(csrc, ccopy)
+    (root / "include").mkdir()
+    shutil.copy(hb.HERE.parent / "include" / "h9g.h", root / "include" / "h9g.h")
+    monkeypatch.setattr(hb, "UNITS", [(ccopy / src.name, own) for src, own in hb.UNITS])
+    bid = hb.build_id()
+    assert bid == h.build_id()
+    copies = hb.deps()
+    assert len(copies) == len(files) and all(root in f.parents for f in copies)
+    for f in copies:
+        old = f.read_bytes()
+        f.write_bytes(old + b"\n")
+        assert hb.build_id() != bid, f.name
+        f.write_bytes(old)
+    assert hb.build_id() == bid
+
+
+def test_isa_same_ends_a_kernel_at_its_symbol():
+    """tools/isa_same.py on a disassembly with the symbols' sizes: the fill
+    after a kernel's end (alignment, and the longer fill after a unit's last
+    kernel) is not compared, so a kernel reads the same wherever in a unit it
+    stands; what lies inside the symbol is, an s_nop included."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("isa_same", bench.ROOT / "tools" / "isa_same.py")
+    isa = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(isa)
+
+    def dis(k2_fill):
+        body = ["\ts_load_dword s0, s[4:5], 0x0    // %012X: C0020002 00000000", "\ts_nop 0    // %012X: BF800000",
+                "\ts_endpgm    // %012X: BF810000"]
+        out, addr = [], 0x1000
+        for name, fill in (("k1", 3), ("k2", k2_fill)):
+            addr = (addr + 255) // 256 * 256
+            out.append("%016x <%s>:" % (addr, name))
+            for ln, size in zip(body + ["\ts_nop 0    // %012X: BF800000"] * fill, [8, 4, 4] + [4] * fill):
+                out.append(ln % addr)
+                addr += size
+        return "\n".join(out) + "\n"
+
+    sizes = {"k1": 16, "k2": 16}
+    code = ["s_load_dword s0, s[4:5], 0x0", "s_nop 0", "s_endpgm"]
+    mid, last = isa.kernels_of_dis(dis(5), sizes), isa.kernels_of_dis(dis(213), sizes)
+    assert mid == last == {"k1": code, "k2": code}
+    assert len(isa.kernels_of_dis(dis(213))["k2"]) == 3 + 213          # (without sizes: up to the next symbol)
+    assert isa.kernels_of_dis(dis(5), {"k1": 16, "k2": 20})["k2"] == code + ["s_nop 0"]
+
+
 def test_pmc_summary_requires_one_build(tmp_path, monkeypatch):
     """tools/pmc_summary.py refuses a profile whose passes ran different
     builds, and records the build of one that did not."""

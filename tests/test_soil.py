@@ -6,7 +6,7 @@ The reference cannot run here (INIT.f90 needs netCDF-Fortran), so parity
 is unpinned against the reference itself: the C restatement
 (oracle/h9_oracle.c h9o_soil_layer/h9o_soil_fmax) is pinned to an
 independent numpy loop written from INIT.f90 (same order of additions),
-and the GPU kernels (hybrid9_amd/csrc/h9g.hip h9g_soil_kernel /
+and the GPU kernels (hybrid9_amd/csrc/h9g_aux.hip h9g_soil_kernel /
 h9g_soil_seq_kernel) are checked bit for bit against the restatement.
 Fixtures: synthetic 30" fields in the BNU storage units (scaled integers,
 plus fractional fields for the sequential-order path) and missing pixels

@@ -18,8 +18,8 @@ def main() -> None:
     if "--c2" in extra:      # config-2 instantiation only (h9g_year.h geo_dispatch, H9G_ONLY_C2): ~1 min
         extra = [e for e in extra if e != "--c2"] + ["-DH9G_ONLY_C2"]
     out = hb.OUT.with_name(f"libh9g_{tag}.so")
-    cmd = [hb.hipcc(), f"--offload-arch={hb.ARCH}", *hb.FLAGS, *extra, hb.id_flag(extra), str(hb.SRC),
-           str(hb.SRC_MON), str(hb.SRC_ET), str(hb.SRC_IO), "-o", str(out)]
+    cmd = [hb.hipcc(), f"--offload-arch={hb.ARCH}", *hb.FLAGS, *extra, hb.id_flag(extra),
+           *[str(src) for src, _ in hb.UNITS], "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.exit(f"{tag}: hipcc failed\n{r.stderr[-3000:]}")

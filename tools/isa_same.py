@@ -8,7 +8,9 @@ disassembly (llvm-objdump -d of a gfx950 code object), or a built library /
 code object, which is unbundled and disassembled here (tools/kernel_meta.py).
 Per kernel the instruction text is compared with what moves without a change
 of the code masked out: comments, addresses and encodings, the __hip_cuid_*
-symbol, local label numbers (renumbered in order of appearance).  Kernels
+symbol, local label numbers (renumbered in order of appearance), and of a
+library or code object the assembler's padding past the end of a kernel's
+symbol.  Kernels
 that are not identical get their opcode-count differences listed, first as
 printed and then with the encoding suffix (_e32, _e64, _dpp, _sdwa) folded,
 and a line-by-line pass says whether they differ in literal operands alone
@@ -92,16 +94,25 @@ def kernels_of_asm(text: str) -> dict[str, list[str]]:
     return {k: norm_labels(v) for k, v in out.items() if v}
 
 
-def kernels_of_dis(text: str) -> dict[str, list[str]]:
-    out, cur = {}, None
+def kernels_of_dis(text: str, sizes: dict[str, int] | None = None) -> dict[str, list[str]]:
+    """sizes: bytes of each kernel's symbol (kernel_meta.code_sizes).  Where given, a kernel ends
+    where its symbol does: what the assembler pads with after it (alignment of the next kernel, and
+    after the last function of a unit's .text the longer fill that guards instruction prefetch) is
+    no code of the kernel's, and which kernel a unit ends with changes when kernels change units."""
+    out, cur, end = {}, None, None
     for line in text.splitlines():
-        m = re.match(r"[0-9a-f]+ <([^>]+)>:", line)
+        m = re.match(r"([0-9a-f]+) <([^>]+)>:", line)
         if m:
-            cur = out.setdefault(m.group(1), [])
+            cur = out.setdefault(m.group(2), [])
+            end = int(m.group(1), 16) + sizes[m.group(2)] if sizes and m.group(2) in sizes else None
             continue
         if cur is None or not line.startswith(("\t", " ")):
             continue
-        ln = line.split("//", 1)[0].strip()
+        ln, _, enc = line.partition("//")
+        a = re.match(r"\s*([0-9A-Fa-f]+):", enc)
+        if end is not None and a and int(a.group(1), 16) >= end:
+            continue
+        ln = ln.strip()
         if ln and ln != "...":      # ("...": zero padding the disassembler elides, after a unit's last kernel)
             cur.append(re.sub(r"\s+", " ", ln))
     return {k: v for k, v in out.items() if v}
@@ -123,7 +134,7 @@ def load(path: Path):
                                      text=True, check=True).stdout
                 notes = subprocess.run([str(kernel_meta.LLVM / "llvm-readelf"), "--notes", str(co)],
                                        capture_output=True, text=True, check=True).stdout
-                ks.update(kernels_of_dis(dis))
+                ks.update(kernels_of_dis(dis, kernel_meta.code_sizes(co)))
                 meta.update(parse_meta(notes))
         return ks, meta
     text = path.read_text(errors="replace")

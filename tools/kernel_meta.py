@@ -27,9 +27,11 @@ BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def code_objects(lib: Path, tmp: Path) -> list[Path]:
     """The gfx950 code object of every device translation unit of the library
-    (h9g.hip's, h9g_mon.hip's and h9g_et.hip's, each with its own instantiations of
-    h9g_year.h's kernels): .hip_fatbin holds one
-    offload bundle per unit, one after the other."""
+    (hybrid9_amd/build.py UNITS: the year kernels' three units, each with its
+    own instantiations of h9g_year.h's kernels, h9g_cols.hip and the host
+    runtime's units with their small kernels), in link order: .hip_fatbin
+    holds one offload bundle per unit, one after the other.  No caller may
+    rely on which unit holds a kernel: look through all of them."""
     fat = tmp / "fat.bin"
     subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib), str(tmp / "x.so")],
                    check=True)
@@ -43,11 +45,6 @@ def code_objects(lib: Path, tmp: Path) -> list[Path]:
                         f"--output={co}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
         out.append(co)
     return out
-
-
-def code_object(lib: Path, tmp: Path) -> Path:
-    """The first unit's (h9g.hip: every kernel but the monthly ones)."""
-    return code_objects(lib, tmp)[0]
 
 
 def kernels(co: Path) -> list[dict]:
