@@ -69,6 +69,23 @@ class _Error(C.Structure):
                 ("day", C.c_int32), ("substep", C.c_int32), ("value", C.c_float)]
 
 
+class _SpinOpts(C.Structure):
+    _fields_ = [("max_cycles", C.c_int32), ("min_cycles", C.c_int32), ("freeze", C.c_int32),
+                ("reserved", C.c_int32), ("tol_water", C.c_double), ("tol_zwt", C.c_double),
+                ("tol_plant", C.c_double)]
+
+
+NSPIN = 6                # H9G_NSPIN: a cycle's history row
+SPIN_HISTORY = ("cells_run", "settled", "stopped", "max_d_water", "max_d_zwt", "max_d_plant")
+
+
+def spin_opts(*, max_cycles, min_cycles=1, tol_water=np.inf, tol_zwt=np.inf, tol_plant=np.inf,
+              freeze=True) -> _SpinOpts:
+    """The ``h9g_spinup_opts`` of Context.spinup."""
+    return _SpinOpts(int(max_cycles), int(min_cycles), int(bool(freeze)), 0, float(tol_water), float(tol_zwt),
+                     float(tol_plant))
+
+
 _lib = None
 _FP = C.POINTER(C.c_float)
 _DP = C.POINTER(C.c_double)
@@ -153,6 +170,11 @@ def lib() -> C.CDLL:
         "h9g_set_monthly": (C.c_int, [vp, C.c_int]),
         "h9g_set_evap": (C.c_int, [vp, C.c_int]),
         "h9g_get_monthly": (C.c_int, [vp, C.c_int, _FP]),
+        "h9g_spinup": (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(_SpinOpts),
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP]),
+        "h9g_spin_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, C.POINTER(C.c_int32),
+                                        C.POINTER(_SpinOpts), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        _DP]),
         "h9g_host_expf": (C.c_float, [C.c_float]),
         "h9g_host_powf": (C.c_float, [C.c_float, C.c_float]),
     }
@@ -225,6 +247,26 @@ def make_config(ncell: int, zi, *, nlayers: int = 8, nisurf: int = 48, grow_on: 
 def config_bytes(cfg: _Config) -> int:
     """Device bytes a context of ``cfg`` allocates (h9g_config_bytes)."""
     return int(lib().h9g_config_bytes(C.byref(cfg)))
+
+
+def spin_selftest(state_prev, state, L: int, k: int, *, err=None, device: int = 0, **opts) -> dict:
+    """One cycle's test of Context.spinup on hand-made packed states one cycle
+    apart, through the same kernel (h9g_spin_selftest): dict(list (the cells
+    still active, increasing), cell_cycle, stats (the history row))."""
+    a = np.ascontiguousarray(state_prev, dtype=np.float32).ravel()
+    b = np.ascontiguousarray(state, dtype=np.float32).ravel()
+    n = a.size // state_size(L)
+    assert a.size == b.size == n * state_size(L)
+    i32 = C.POINTER(C.c_int32)
+    e = None if err is None else np.ascontiguousarray(err, dtype=np.int32)
+    lst, cc = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+    st = np.zeros(NSPIN + 1, np.float64)
+    o = spin_opts(**opts)
+    rc = lib().h9g_spin_selftest(int(device), n, int(L), _fp(a), _fp(b), None if e is None else e.ctypes.data_as(i32),
+                                 C.byref(o), int(k), lst.ctypes.data_as(i32), cc.ctypes.data_as(i32),
+                                 st.ctypes.data_as(_DP))
+    _check(rc, "h9g_spin_selftest")
+    return dict(list=lst[:int(st[NSPIN])].copy(), cell_cycle=cc, stats=st[:NSPIN].copy())
 
 
 class Context:
@@ -393,6 +435,38 @@ class Context:
         if rc and raise_on_stop:
             raise ReferenceStop(self.last_error())
         return out, [int(v) for v in np_][:len(decades(jyear0, sl.size))]
+
+    def spinup(self, slots, jyear0: int, *, max_cycles: int, min_cycles: int = 1, tol_water=np.inf,
+               tol_zwt=np.inf, tol_plant=np.inf, freeze: bool = True, raise_on_stop: bool = True) -> dict:
+        """Spin-up to equilibrium (h9g_spinup): repeats years jyear0 ..
+        jyear0+len(slots)-1 (isolated cells, the forcing of year jyear0+k
+        resident in slots[k]) and tests every cell after each cycle against
+        its own state one cycle earlier: a cell settles once its column water
+        (mm), water table (mm) and relative plant-mass drifts are within the
+        tolerances (inf: criterion off; 0: a bit-exact fixed point).  freeze:
+        a settled cell leaves the later cycles (bit-exact for the others, cells
+        being independent); else every cell runs every cycle.  Synchronous.
+        Returns dict(cycles, cell_cycle (ncell int32: k > 0 settled at cycle k,
+        0 still active, -1 masked or stopped before, -2 stopped during the
+        call), history (cycles, 6: SPIN_HISTORY), rc (the STOP code))."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        opts = spin_opts(max_cycles=max_cycles, min_cycles=min_cycles, tol_water=tol_water, tol_zwt=tol_zwt,
+                         tol_plant=tol_plant, freeze=freeze)
+        cyc = C.c_int32(0)
+        cc = np.zeros(self.ncell, dtype=np.int32)
+        hist = np.zeros((max(int(max_cycles), 1), NSPIN), dtype=np.float64)
+        i32 = C.POINTER(C.c_int32)
+        rc = self._lib.h9g_spinup(self._h, sl.ctypes.data_as(i32), int(jyear0), int(sl.size), C.byref(opts),
+                                  C.byref(cyc), cc.ctypes.data_as(i32), hist.ctypes.data_as(_DP))
+        if rc == -1:
+            raise ValueError("spinup: bad slots (distinct, resident, one per year), years or options")
+        if rc == -4:
+            raise H9GError("h9g_spinup: H9G_ESTATE: spin-up records nothing (turn daily and monthly recording "
+                           "off) and needs parameters and a state")
+        _check(rc, "h9g_spinup")
+        if rc and raise_on_stop:
+            raise ReferenceStop(self.last_error())
+        return dict(cycles=int(cyc.value), cell_cycle=cc, history=hist[:cyc.value].copy(), rc=rc)
 
     def ordered_stats(self) -> dict:
         """How the last ordered call overlapped its decades (h9g_ordered_stats)."""
@@ -789,7 +863,7 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
         state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False,
-        evap=False):
+        evap=False, spinup: dict | None = None):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -803,21 +877,40 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     snapshots (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n).
     evap: evapotranspiration recording (Context.set_evap): row evap (3) of
     annual and monthly is the year's evaporation sum instead of the
-    reference's zero."""
+    reference's zero.  spinup: dict(years=Y, max_cycles=..., and the other
+    keywords of Context.spinup): the first Y years of ``forcing``, resident in
+    Y slots, are cycled to equilibrium before the run proper (Context.spinup;
+    nothing is recorded meanwhile) -> out["spinup"]; the years of the run
+    proper are unchanged and start from the spun-up state.  A STOP during
+    spin-up takes that cell out of the run and is reported in out["spinup"]
+    (rc) and in ``errors``."""
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
-    with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device) as ctx:
+    spin = dict(spinup) if spinup else None
+    spin_years = int(spin.pop("years")) if spin else 0
+    if spin and not 1 <= spin_years <= nyears:
+        raise ValueError("run: spinup['years'] must be between 1 and nyears")
+    with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device,
+                 nslots=max(2, spin_years)) as ctx:
         ctx.set_params(params)
         if state0 is None:
             ctx.init_state()
         else:
             ctx.set_state(state0)
+        if evap:
+            ctx.set_evap(True)
+        spun = None
+        if spin:
+            d0 = 0
+            for k in range(spin_years):
+                nt = days_in_year(year0 + k)
+                ctx.push_forcing(k, forcing[:, d0:d0 + nt, :])
+                d0 += nt
+            spun = ctx.spinup(list(range(spin_years)), year0, raise_on_stop=False, **spin)
         if daily_cells is not None:
             ctx.set_daily(daily_cells)
         if monthly:
             ctx.set_monthly(True)
-        if evap:
-            ctx.set_evap(True)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
         d0, rc, err, daily = 0, 0, None, []
@@ -841,4 +934,6 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             out["daily"] = np.concatenate(daily)
         if monthly:
             out["monthly"] = mon
+        if spun is not None:
+            out["spinup"] = spun
         return out

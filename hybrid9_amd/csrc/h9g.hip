@@ -32,8 +32,9 @@
 // runtime's core (h9g_ctx.h): the context's lifetime and configuration,
 // parameters, state, forcing and prefetch, the year launch with its
 // permutation and diagnostics kernels, h9g_run_year, the daily and monthly
-// recording, statistics and errors.  The ordered mode is h9g_ord.hip; the
-// soil build, synthetic inputs and self-tests are h9g_aux.hip.
+// recording, statistics and errors.  The ordered mode is h9g_ord.hip, spin-up
+// h9g_spin.hip; the soil build, synthetic inputs and self-tests are
+// h9g_aux.hip.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -217,6 +218,7 @@ void h9g_destroy(h9g_ctx *ctx) {
   (void)hipFree(ctx->d_daily);
   (void)hipFree(ctx->d_fyrs);
   ord_free(ctx);
+  spin_free(ctx);
   for (auto e : ctx->ev_copied) hipEventDestroy(e);
   for (auto e : ctx->ev_consumed) hipEventDestroy(e);
   for (int i = 0; i < NEVT; i++) {

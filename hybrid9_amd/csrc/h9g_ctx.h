@@ -1,8 +1,8 @@
 // h9g_ctx.h -- what the host runtime's units share (not ABI): the context,
 // the year launch's description and the few functions that cross units.
 // Included by h9g.hip (context, forcing, the year launch, recording),
-// h9g_ord.hip (the ordered mode) and h9g_aux.hip (soil build, synthetic
-// inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
+// h9g_ord.hip (the ordered mode), h9g_spin.hip (spin-up) and h9g_aux.hip (soil
+// build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
 // h9g_et.hip, h9g_cols.hip) do not include it: a change here recompiles no
 // geometry-templated kernel.  Their launchers are declared in h9g_year.h.
 #pragma once
@@ -114,6 +114,7 @@ struct h9g_ctx {
   // evapotranspiration output (h9g_set_evap; the ET kernels): row evap of the
   // annual and monthly rows is the year's evaporation sum.  No buffer of its own.
   int evap = 0;
+  struct SpinBufs *spin = nullptr;   // h9g_spinup's buffers (h9g_spin.hip); null until its first call
 };
 
 // One year launch (run_year_impl).
@@ -157,4 +158,6 @@ H9G_LOCAL int mon_begin(h9g_ctx *ctx, int nyears);
 H9G_LOCAL int diag_launch(h9g_ctx *ctx);
 // h9g_ord.hip
 H9G_LOCAL void ord_free(h9g_ctx *ctx);
+// h9g_spin.hip
+H9G_LOCAL void spin_free(h9g_ctx *ctx);
 }

@@ -30,7 +30,42 @@ TYPE, BIND(C) :: h9g_error
   REAL(C_FLOAT) :: value
 END TYPE h9g_error
 
+! h9g_spinup's options (include/h9g.h): a cell settles at cycle k >=
+! min_cycles once its column water (mm), water table (mm) and relative
+! plant-mass drifts over a cycle are within the tolerances.
+INTEGER, PARAMETER :: H9G_NSPIN = 6
+TYPE, BIND(C) :: h9g_spinup_opts
+  INTEGER(C_INT32_T) :: max_cycles, min_cycles, freeze, reserved
+  REAL(C_DOUBLE) :: tol_water, tol_zwt, tol_plant
+END TYPE h9g_spinup_opts
+
 INTERFACE
+  ! Spin-up to equilibrium: years jyear0 .. jyear0+nyears-1 (isolated cells,
+  ! the forcing of year jyear0+k resident in slots(k+1)) repeated until the
+  ! cells settle; history (H9G_NSPIN, max_cycles).
+  FUNCTION h9g_spinup (ctx, slots, jyear0, nyears, opts, cycles_run, cell_cycle, history) &
+           BIND(C, NAME='h9g_spinup')
+    IMPORT :: C_PTR, C_INT, C_INT32_T, C_DOUBLE, h9g_spinup_opts
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT32_T), INTENT(IN) :: slots (*)
+    INTEGER(C_INT), VALUE :: jyear0, nyears
+    TYPE(h9g_spinup_opts), INTENT(IN) :: opts
+    INTEGER(C_INT32_T), INTENT(OUT) :: cycles_run
+    INTEGER(C_INT32_T), INTENT(OUT) :: cell_cycle (*)
+    REAL(C_DOUBLE), INTENT(OUT) :: history (*)
+    INTEGER(C_INT) :: h9g_spinup
+  END FUNCTION
+  FUNCTION h9g_spin_selftest (device, n, L, state_prev, state, err, opts, k, list, &
+                              cell_cycle, stats) BIND(C, NAME='h9g_spin_selftest')
+    IMPORT :: C_INT, C_INT32_T, C_FLOAT, C_DOUBLE, h9g_spinup_opts
+    INTEGER(C_INT), VALUE :: device, n, L, k
+    REAL(C_FLOAT), INTENT(IN) :: state_prev (*), state (*)
+    INTEGER(C_INT32_T), INTENT(IN) :: err (*)
+    TYPE(h9g_spinup_opts), INTENT(IN) :: opts
+    INTEGER(C_INT32_T), INTENT(OUT) :: list (*), cell_cycle (*)
+    REAL(C_DOUBLE), INTENT(OUT) :: stats (*)
+    INTEGER(C_INT) :: h9g_spin_selftest
+  END FUNCTION
   FUNCTION h9g_abi_version () BIND(C, NAME='h9g_abi_version')
     IMPORT :: C_INT
     INTEGER(C_INT) :: h9g_abi_version

@@ -55,6 +55,22 @@ PROGRAM H9_HOST
 ! mxyYYYY.nc (then written by h9g_write_mxy_nc_evap) is the year's evaporation
 ! sum instead of the reference's zero, in both cell_order settings.
 !
+! spinup_cycles > 0 (0 = off, the default) spins the cold start of
+! INIT.f90:707-811 up to equilibrium before the run proper (h9g_spinup,
+! DESIGN.md §7): the run's first spinup_years years (default 1) are staged
+! into their own slots and repeated, isolated cells, at most spinup_cycles
+! times; a cell settles at a cycle >= spinup_min_cycles (default 1) once its
+! column water and water table drifts over a cycle are within spinup_tol_water
+! and spinup_tol_zwt (mm) and its relative plant-mass drift within
+! spinup_tol_plant (defaults: a huge value, criterion off); spinup_freeze = 1
+! (default) takes a settled cell out of the later cycles.  In either
+! cell_order setting: spin-up only produces the start state of the run proper,
+! whose years are unchanged.  Writes <out_dir>/spinup.txt, one line per cycle
+! (cycle, cells run, settled, stopped, the maxima of the three drifts), and
+! <out_dir>/spinup_cycle.i32 (ncell int32: the cycle each cell settled at, 0
+! still active, -1 never ran, -2 stopped).  A STOP during spin-up ends the
+! program after both files are written.
+!
 ! Usage:  h9_host [driver.txt] [h9gpu.nml]
 ! Outputs: <out_dir>/annual.f32 (ncell, 12+L, nyears),
 !          <out_dir>/state_end.f32 (packed state, include/h9g.h) and, on a
@@ -76,10 +92,14 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
 INTEGER :: cell_order, ordered_decades, daily, monthly, evap
+INTEGER :: spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze
+REAL(C_DOUBLE) :: spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 INTEGER(C_INT64_T) :: seed
 NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
-                 cell_order, ordered_decades, daily, monthly, evap
+                 cell_order, ordered_decades, daily, monthly, evap, &
+                 spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze, &
+                 spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
 TYPE(C_PTR) :: pgf_ptr (7)
 CHARACTER (LEN = *), PARAMETER :: pgf_var (7) = &
@@ -117,6 +137,11 @@ REAL :: a_lon, b_lon, a_lat, b_lat, lon1, lat1
 REAL(C_FLOAT), ALLOCATABLE :: mon (:,:,:)
 INTEGER(C_INT64_T), ALLOCATABLE :: mgid (:)
 INTEGER :: mnx, mny
+! --- spin-up (h9g_spinup) ---------------------------------------------------
+TYPE(h9g_spinup_opts) :: sopts
+INTEGER(C_INT32_T) :: scycles
+INTEGER(C_INT32_T), ALLOCATABLE :: sslots (:), scell (:)
+REAL(C_DOUBLE), ALLOCATABLE :: shist (:,:)
 
 !----------------------------------------------------------------------!
 ! Defaults, then driver.txt and h9gpu.nml.
@@ -125,6 +150,8 @@ input_mode = 'synth'; case_dir = ''; out_dir = '.'; pgf_dir = '.'
 nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
 monthly = 0; evap = 0
+spinup_cycles = 0; spinup_years = 1; spinup_min_cycles = 1; spinup_freeze = 1
+spinup_tol_water = HUGE (1.0D0); spinup_tol_zwt = HUGE (1.0D0); spinup_tol_plant = HUGE (1.0D0)
 daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
 PATH_output = '.'
 seed = 20161123_C_INT64_T
@@ -261,6 +288,10 @@ IF (cell_order /= 0) THEN                  ! the reference's order: every year o
   IF (daily /= 0) ordered_decades = 1      ! recorded runs: one h9g_run_decade_ordered per decade
   IF (ordered_decades > 0) nslot = MIN (nyears, 10 * ordered_decades)
 END IF
+IF (spinup_cycles > 0) THEN                ! the spin-up period resident too
+  IF (spinup_years < 1 .OR. spinup_years > nyears) STOP 'h9_host: spinup_years must be in 1 .. nyears'
+  nslot = MAX (nslot, spinup_years)
+END IF
 cfg%ncell = ncell
 cfg%nlayers = L
 cfg%nisurf = NISURF
@@ -290,6 +321,42 @@ ELSE
   CALL chk (h9g_set_cells (ctx, gid, lat))
   CALL chk (h9g_synth_params (ctx, seed))
   CALL chk (h9g_init_state (ctx))
+END IF
+
+!----------------------------------------------------------------------!
+! Spin-up: the run's first spinup_years years repeated until the cells
+! settle (h9g_spinup); the run proper then starts from that state.
+!----------------------------------------------------------------------!
+IF (spinup_cycles > 0) THEN
+  ALLOCATE (sslots (spinup_years), scell (ncell), shist (H9G_NSPIN, spinup_cycles))
+  d0 = 1
+  DO k = 1, spinup_years
+    sslots (k) = k - 1
+    CALL stage (k - 1, year0 + k - 1, d0)
+    d0 = d0 + time_BOY (year0+k-1859) - time_BOY (year0+k-1-1859)
+  END DO
+  sopts%max_cycles = spinup_cycles
+  sopts%min_cycles = spinup_min_cycles
+  sopts%freeze = spinup_freeze
+  sopts%reserved = 0
+  sopts%tol_water = spinup_tol_water
+  sopts%tol_zwt = spinup_tol_zwt
+  sopts%tol_plant = spinup_tol_plant
+  IF (evap /= 0) CALL chk (h9g_set_evap (ctx, 1))
+  rc = h9g_spinup (ctx, sslots, year0, spinup_years, sopts, scycles, scell, shist)
+  IF (rc < 0) CALL h9g_check_stop (ctx, rc)
+  OPEN (NEWUNIT = u, FILE = TRIM (out_dir)//'/spinup.txt', STATUS = 'REPLACE')
+  DO k = 1, scycles
+    WRITE (u,'(I5,3I10,3ES24.16)') k, NINT (shist (1:3, k)), shist (4:6, k)
+  END DO
+  CLOSE (u)
+  OPEN (NEWUNIT = u, FILE = TRIM (out_dir)//'/spinup_cycle.i32', ACCESS = 'STREAM', &
+        FORM = 'UNFORMATTED', STATUS = 'REPLACE')
+  WRITE (u) scell
+  CLOSE (u)
+  WRITE (*,'(A,I5,A,I8,A,I8,A)') ' spin-up:', scycles, ' cycles,', COUNT (scell > 0), ' cells settled,', &
+        COUNT (scell == 0), ' still active'
+  CALL h9g_check_stop (ctx, rc)
 END IF
 
 !----------------------------------------------------------------------!

@@ -312,6 +312,88 @@ int h9g_get_monthly(h9g_ctx *ctx, int k, float *out);
  * context.  h9g_kernel_name then reports the ET kernel. */
 int h9g_set_evap(h9g_ctx *ctx, int on);
 
+/* --- spin-up to equilibrium: cycle a forcing period, retire settled cells - */
+/* The model cold-starts from INIT.f90:707-811, and the reference's only
+ * answer is to repeat years (its LCLIM loop re-reads the site years
+ * NYR_SPIN_UP times).  h9g_spinup repeats a forcing period on the device
+ * until the cells stop changing, tests every cell on its own, and with
+ * freeze = 1 launches only the cells that have not settled yet.
+ *
+ * A cycle runs years jyear0 .. jyear0+nyears-1 as h9g_run_year runs them
+ * (isolated cells: every cell its own smp), the forcing of year jyear0+k in
+ * slots[k]; every cycle the same calendar years.  The slots are distinct and
+ * stay resident for the whole call (H9G_EINVAL otherwise, as
+ * h9g_run_ordered).
+ *
+ * After cycle k = 1, 2, ... every cell that ran it is tested against its own
+ * state one cycle earlier (cycle 0: the state the call found).  In double,
+ * from the f32 state, one IEEE operation per step:
+ *   W   = h2osoi_liq(1) + ... + h2osoi_liq(L), added in that order, then + wa
+ *   d_w = |W_k - W_{k-1}|                                   (mm)
+ *   d_z = |zwt_k - zwt_{k-1}|                               (mm)
+ *   d_p = 0 if pm_k == pm_{k-1}, else |pm_k - pm_{k-1}| / |pm_{k-1}|
+ *         (plant_mass; +inf from a zero pm_{k-1})
+ * The cell settles at cycle k when k >= min_cycles, d_w <= tol_water,
+ * d_z <= tol_zwt and d_p <= tol_plant; a NaN drift never settles.  A
+ * tolerance of +inf turns its criterion off, 0 demands a bit-exact fixed
+ * point of that quantity.  H9G_EINVAL for a negative or NaN tolerance,
+ * max_cycles < 1, min_cycles < 1 or > max_cycles, freeze not 0 or 1, or
+ * reserved not 0.
+ *
+ * freeze = 1: a settled cell keeps the state, annual means and STOP record
+ * its last cycle left and is not launched again; the later cycles are list
+ * launches of the cells still active (cells in increasing order; the kernel
+ * by the list's length, as the cell order's re-runs).  Cells are independent,
+ * so every other cell's bits are what they would be with it running.  The
+ * call ends after the first cycle that leaves no active cell, or after
+ * max_cycles.
+ * freeze = 0: every cycle is an every-cell launch, cell_cycle records the
+ * first cycle at which the cell met the criterion, and the call ends after
+ * the first cycle in which every tested cell meets it, or after max_cycles;
+ * the end state is that of cycles_run x nyears h9g_run_year calls, bit for
+ * bit.
+ *
+ * A cell that reaches a reference STOP in a cycle leaves the run (the year
+ * kernels skip it); the others go on.  A masked cell, or one that had stopped
+ * before the call, never runs.  Returns 0, or the code of the first STOP in
+ * context order, as h9g_sync (h9g_last_error: that cell's record, with the
+ * year of the cycle it stopped in).
+ *   cycles_run    cycles run (may be NULL)
+ *   cell_cycle[c] (ncell, may be NULL)  k > 0: settled at cycle k; 0: still
+ *                 active when the call ended; -1: masked or stopped before the
+ *                 call; -2: stopped during the call
+ *   history       (max_cycles, H9G_NSPIN), may be NULL; row k-1 of cycle k:
+ *                 cells run, cells settled at k (freeze = 0: that met the
+ *                 criterion for the first time), cells stopped in k, then the
+ *                 maxima of d_w, d_z and d_p over the cells tested in k (0
+ *                 with none; a NaN drift is not counted).  Rows of cycles not
+ *                 run are 0.
+ * After the call h9g_get_state holds every cell's state after the last cycle
+ * it ran, h9g_get_annual the means of the last year of that cycle, and
+ * h9g_get_diagnostics is recomputed once over exactly those rows;
+ * h9g_launch_stats counts the launches as usual.
+ * Spin-up records nothing: H9G_ESTATE with a daily selection or monthly
+ * recording on.  ET recording (h9g_set_evap) is allowed.  Synchronous.  One
+ * small kernel (h9g_spin_kernel) and one read of eight doubles per cycle;
+ * three doubles and three int32 per cell of device memory, allocated by the
+ * first call and released with the context (not part of h9g_config_bytes).
+ * Without a call nothing is added anywhere: no launch, allocation or
+ * synchronisation. */
+typedef struct {
+  int32_t max_cycles;   /* >= 1 */
+  int32_t min_cycles;   /* >= 1: no cell settles before this cycle */
+  int32_t freeze;       /* 1: a settled cell leaves the later cycles; 0: every cell runs every cycle */
+  int32_t reserved;     /* 0 */
+  double tol_water;     /* mm: |W_k - W_{k-1}|, W = sum_i h2osoi_liq(i) + wa */
+  double tol_zwt;       /* mm: |zwt_k - zwt_{k-1}| */
+  double tol_plant;     /* relative: |pm_k - pm_{k-1}| / |pm_{k-1}| (plant_mass) */
+} h9g_spinup_opts;
+#define H9G_NSPIN 6
+int h9g_spinup(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears,
+               const h9g_spinup_opts *opts, int32_t *cycles_run,
+               int32_t *cell_cycle /* ncell, may be NULL */,
+               double *history /* max_cycles x H9G_NSPIN, may be NULL */);
+
 /* --- outputs (HYBRID9.f90:263-290) ------------------------------------ */
 /* Annual means of the last year run, (12+L) rows of (ncell):
  * npp plant_mass rnf evap tas rlds rsds huss ps pr rhs theta(1..L)
@@ -435,6 +517,16 @@ int h9g_math_fast_selftest(int device, int n, const float *x, const float *y,
  * the IEEE division (subnormal or NaN quotient). */
 int h9g_div_selftest(int device, int n, const float *x, const float *d,
                      float *out, int *flag);
+/* One cycle's test of h9g_spinup on hand-made states, through the same kernel
+ * (h9g_spin_kernel): n cells of L layers, none masked; state_prev and state
+ * are packed states (h9g_get_state's layout) one cycle apart, err (n, may be
+ * NULL) the STOP code of each cell after the cycle (non-zero: it stopped in
+ * it), k the cycle's number.  list (n) receives the cells still active, in
+ * increasing order, cell_cycle (n) as h9g_spinup's, stats (H9G_NSPIN + 1) the
+ * cycle's history row, then the list's length. */
+int h9g_spin_selftest(int device, int n, int L, const float *state_prev, const float *state,
+                      const int32_t *err, const h9g_spinup_opts *opts, int k,
+                      int32_t *list, int32_t *cell_cycle, double *stats);
 /* Hardware ids as the pair kernel's issue pacer decodes them: nblocks
  * workgroups of the pair kernel's shape and LDS size; per wave out[3w..3w+2]
  * = HW_REG_HW_ID, HW_REG_XCC_ID, 1 if every wave was resident at once. */
