@@ -28,6 +28,10 @@ NANNUAL_SCALARS = 11
 NDIAG = 12
 NDAILY = 11              # H9G_NDAILY: the daily diagnostics line (site.DIAG_FIELDS)
 NMONTHS = 12             # H9G_NMONTHS
+NDAYREC = 7              # H9G_NDAYREC: the day record (DAY_FIELDS)
+# The rows of a day record (Context.get_days); rnf_sum and evap_sum are the
+# year's running sums (day_values differences them).
+DAY_FIELDS = ("rnf_sum", "evap_sum", "soil_water", "theta1", "zwt", "wa", "LAI")
 ANNUAL_SCALARS = ("npp", "plant_mass", "rnf", "evap", "tas", "rlds", "rsds",
                   "huss", "ps", "pr", "rhs")
 DIAG_NAMES = ("cells", "rnf_sum", "theta_total_sum", "zwt_sum", "wa_sum",
@@ -170,6 +174,10 @@ def lib() -> C.CDLL:
         "h9g_set_monthly": (C.c_int, [vp, C.c_int]),
         "h9g_set_evap": (C.c_int, [vp, C.c_int]),
         "h9g_get_monthly": (C.c_int, [vp, C.c_int, _FP]),
+        "h9g_set_days": (C.c_int, [vp, C.c_int]),
+        "h9g_get_days": (C.c_int, [vp, C.c_int, _FP]),
+        "h9g_write_dxy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _FP, C.c_int, _I64P, C.c_int, C.c_int,
+                                       _FP]),
         "h9g_spinup": (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(_SpinOpts),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP]),
         "h9g_spin_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, C.POINTER(C.c_int32),
@@ -461,8 +469,8 @@ class Context:
         if rc == -1:
             raise ValueError("spinup: bad slots (distinct, resident, one per year), years or options")
         if rc == -4:
-            raise H9GError("h9g_spinup: H9G_ESTATE: spin-up records nothing (turn daily and monthly recording "
-                           "off) and needs parameters and a state")
+            raise H9GError("h9g_spinup: H9G_ESTATE: spin-up records nothing (turn daily, monthly and day "
+                           "recording off) and needs parameters and a state")
         _check(rc, "h9g_spinup")
         if rc and raise_on_stop:
             raise ReferenceStop(self.last_error())
@@ -589,6 +597,33 @@ class Context:
         if rc == -4:
             raise H9GError("h9g_get_monthly: nothing recorded (H9G_ESTATE): set_monthly(), then run")
         _check(rc, "h9g_get_monthly")
+        return out
+
+    # -- day records: day-end records of every cell -------------------------
+    def set_days(self, on: bool = True):
+        """Turns day recording on or off (h9g_set_days; off by default).  It
+        rides on evapotranspiration recording: set_evap() first (H9G_ESTATE
+        otherwise, and from set_evap(False) while it is on).  With it on every
+        year launch runs the day year kernels, which also store NDAYREC values
+        per cell and day (DAY_FIELDS); annual means, month-end snapshots,
+        state, STOP records and daily lines are the bits of an ET run."""
+        rc = self._lib.h9g_set_days(self._h, int(bool(on)))
+        if rc == -4:
+            raise H9GError("h9g_set_days: H9G_ESTATE: day recording needs set_evap() first")
+        _check(rc, "h9g_set_days")
+
+    def get_days(self, k: int = 0) -> np.ndarray:
+        """The day records of year k (0-based) of the last run_year (k = 0)
+        or ordered call: (nday_k, 7, ncell) float32 in DAY_FIELDS' order
+        (h9g_get_days; NaN from a cell's STOP day on and for a masked cell).
+        ``day_values`` turns the two running sums into the days' amounts."""
+        years = getattr(self, "daily_years", [])
+        nt = days_in_year(years[k]) if 0 <= k < len(years) else 366
+        out = np.empty((nt, NDAYREC, self.ncell), dtype=np.float32)
+        rc = self._lib.h9g_get_days(self._h, int(k), _fp(out))
+        if rc == -4:
+            raise H9GError("h9g_get_days: nothing recorded (H9G_ESTATE): set_evap(), set_days(), then run")
+        _check(rc, "h9g_get_days")
         return out
 
     def sync(self, raise_on_stop: bool = True) -> int:
@@ -720,6 +755,35 @@ def write_mxy_nc(path, snapshots, gid, zc, jyear: int, nisurf: int, nx: int = 72
                                 int(jyear), int(nisurf), _fp(snapshots)), name)
 
 
+def day_values(records) -> np.ndarray:
+    """A year's day records (nday, 7, ncell) (Context.get_days) with the two
+    running sums turned into the days' amounts: rows 0 (runoff) and 1
+    (evapotranspiration) become, in float64, S[d] - S[d-1] with S[-1] = 0,
+    rounded to float32, in mm per day; rows 2..6 are unchanged.  Derived from
+    the reference's f32 running sums: deterministic, but not a reference
+    quantity.  NaN days (a STOP, a masked cell) stay NaN."""
+    r = np.asarray(records, dtype=np.float32)
+    if r.ndim != 3 or r.shape[1] != NDAYREC:
+        raise ValueError("day_values: records must be (nday, 7, ncell)")
+    out = np.array(r, dtype=np.float32)
+    s = r[:, :2].astype(np.float64)
+    out[:, :2] = np.diff(s, axis=0, prepend=np.zeros_like(s[:1])).astype(np.float32)
+    return out
+
+
+def write_dxy_nc(path, records, gid, zc, jyear: int, nx: int = 720, ny: int = 360):
+    """One year of day records (nday, 7, ncell) of the cells gid, as
+    ``day_values`` derives them, to dxyYYYY.nc: seven variables under a leading
+    dimension time on write_axy_nc's grid (h9g_write_dxy_nc; netCDF classic,
+    64-bit offsets)."""
+    records = np.ascontiguousarray(records, dtype=np.float32)
+    gid = np.ascontiguousarray(gid, dtype=np.int64)
+    zc = np.ascontiguousarray(zc, dtype=np.float32)
+    assert records.ndim == 3 and records.shape[1:] == (NDAYREC, gid.size)
+    _check(lib().h9g_write_dxy_nc(str(path).encode(), nx, ny, zc.size, _fp(zc), gid.size, gid.ctypes.data_as(_I64P),
+                                  int(jyear), records.shape[0], _fp(records)), "h9g_write_dxy_nc")
+
+
 def month_ends(jyear: int) -> np.ndarray:
     """The last day (1-based) of each month of jyear, INIT.f90:844-859."""
     e = np.array([31, 59, 90, 120, 151, 181, 212, 243, 273, 304, 334, 365])
@@ -764,7 +828,7 @@ def decades(year0: int, nyears: int):
 
 def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                    state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None,
-                   monthly=False, evap=False):
+                   monthly=False, evap=False, days=False):
     """``run`` in the reference's own cell order (smp carried from cell to
     cell, cells in the given order; chains: a reference rank per cell, each
     rank its own chain, shard.reference_blocks).  pipelined: one
@@ -777,7 +841,10 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
     decades then run one after another.  monthly: the month-end snapshots
     (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n); the decades
     stay overlapped.  evap: evapotranspiration recording (Context.set_evap):
-    row evap of annual and monthly is the year's evaporation sum."""
+    row evap of annual and monthly is the year's evaporation sum.  days: day
+    records (Context.set_days; turns evap on) -> out["days"] (nyears, 366, 7,
+    n), day 366 of a 365-day year NaN; the decades stay overlapped."""
+    evap = evap or days
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device,
@@ -790,6 +857,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             ctx.set_monthly(True)
         if evap:
             ctx.set_evap(True)
+        if days:
+            ctx.set_days(True)
         if state0 is None:
             ctx.init_state()
         else:
@@ -811,13 +880,15 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
                     out["daily"] = np.concatenate([ctx.get_daily(k) for k in range(nyears)])
                 if monthly:
                     out["monthly"] = np.stack([ctx.get_monthly(k) for k in range(nyears)])
+                if days:
+                    out["days"] = _days_years(ctx, nyears)
                 return out
     if pipelined:
         # a STOP: the reference program ends in that decade, while run_ordered
         # goes on with the other cells; the decade-by-decade form stops there
         return run_cell_order(zi=zi, params=params, forcing=forcing, nisurf=nisurf, year0=year0, nyears=nyears,
                               grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False,
-                              daily_cells=daily_cells, monthly=monthly, evap=evap)
+                              daily_cells=daily_cells, monthly=monthly, evap=evap, days=days)
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device, nslots=10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
@@ -827,12 +898,15 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             ctx.set_monthly(True)
         if evap:
             ctx.set_evap(True)
+        if days:
+            ctx.set_days(True)
         if state0 is None:
             ctx.init_state()
         else:
             ctx.set_state(state0)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
+        rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if days else None
         d0, rc, err, passes, work, daily = 0, 0, None, [], [], []
         for y0, ny in decades(year0, nyears):
             for k in range(ny):
@@ -848,6 +922,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             if monthly:
                 for k in range(ny):
                     mon[y0 - year0 + k] = ctx.get_monthly(k)
+            if days:
+                rec[y0 - year0:y0 - year0 + ny] = _days_years(ctx, ny)
             rc = ctx.decade_rc
             if rc:
                 err = ctx.last_error()
@@ -858,12 +934,23 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             out["daily"] = np.concatenate(daily)
         if monthly:
             out["monthly"] = mon
+        if days:
+            out["days"] = rec
         return out
+
+
+def _days_years(ctx, nyears: int) -> np.ndarray:
+    """Years 0 .. nyears-1 of the context's day records as (nyears, 366, 7, n)."""
+    rec = np.full((nyears, 366, NDAYREC, ctx.ncell), np.nan, dtype=np.float32)
+    for k in range(nyears):
+        d = ctx.get_days(k)
+        rec[k, :d.shape[0]] = d
+    return rec
 
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
         state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False,
-        evap=False, spinup: dict | None = None):
+        evap=False, spinup: dict | None = None, days=False):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -877,13 +964,16 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     snapshots (Context.set_monthly) -> out["monthly"] (nyears, 12, 12+L, n).
     evap: evapotranspiration recording (Context.set_evap): row evap (3) of
     annual and monthly is the year's evaporation sum instead of the
-    reference's zero.  spinup: dict(years=Y, max_cycles=..., and the other
+    reference's zero.  days: day records (Context.set_days; turns evap on)
+    -> out["days"] (nyears, 366, 7, n) in DAY_FIELDS' order, day 366 of a
+    365-day year NaN.  spinup: dict(years=Y, max_cycles=..., and the other
     keywords of Context.spinup): the first Y years of ``forcing``, resident in
     Y slots, are cycled to equilibrium before the run proper (Context.spinup;
     nothing is recorded meanwhile) -> out["spinup"]; the years of the run
     proper are unchanged and start from the spun-up state.  A STOP during
     spin-up takes that cell out of the run and is reported in out["spinup"]
     (rc) and in ``errors``."""
+    evap = evap or days
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
     spin = dict(spinup) if spinup else None
@@ -911,8 +1001,11 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             ctx.set_daily(daily_cells)
         if monthly:
             ctx.set_monthly(True)
+        if days:
+            ctx.set_days(True)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
+        rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if days else None
         d0, rc, err, daily = 0, 0, None, []
         for y in range(nyears):
             nt = days_in_year(year0 + y)
@@ -924,6 +1017,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                 daily.append(ctx.get_daily())
             if monthly:
                 mon[y] = ctx.get_monthly()
+            if days:
+                rec[y, :nt] = ctx.get_days()
             d0 += nt
             if rc:
                 err = ctx.last_error()
@@ -934,6 +1029,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             out["daily"] = np.concatenate(daily)
         if monthly:
             out["monthly"] = mon
+        if days:
+            out["days"] = rec
         if spun is not None:
             out["spinup"] = spun
         return out

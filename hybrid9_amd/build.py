@@ -29,6 +29,7 @@ UNITS = [
     (CSRC / "h9g_plain.hip", []),   # the plain year kernels (h9g_year.h)
     (CSRC / "h9g_mon.hip", []),     # the monthly kernels: the same kernels with the Months policy
     (CSRC / "h9g_et.hip", []),      # the ET kernels: the same kernels with the EvapProf and MonthsEt policies
+    (CSRC / "h9g_day.hip", []),     # the day-record kernels: the same kernels with the EvapProf and DaysEt policies
     (CSRC / "h9g_cols.hip", []),    # the other geometry-templated kernels: init, sort, site, focus
     (CSRC / "h9g_io.cpp", [ID]),    # host-only NetCDF I/O, and h9g_build_id
 ]
@@ -104,7 +105,7 @@ def _run(cmd, verbose):
 def build(force: bool = False, verbose: bool = False, extra=()) -> Path:
     """Compiles the translation units of UNITS to objects, side by side, each
     only when its own inputs changed (keyed by the digest of its flags, its
-    source and the headers it includes), and links libh9g.so.  The three units
+    source and the headers it includes), and links libh9g.so.  The four units
     of year kernels take minutes each and h9g_cols.hip about one; the host
     runtime's units and the I/O take seconds, so a change there is a short build."""
     if not force and up_to_date():

@@ -167,7 +167,7 @@ static std::string year_kernel_name(const h9g_ctx *ctx, int kind, size_t cells) 
   const std::string targs = "<" + L + "," + (gk == GEO_R ? "GeoR" : "GeoC<" + L + "," + std::to_string((int)gk) + ">") + ">";
   auto name = [&](int k) {
     const ShapeInfo si = shape_info(year_shape(k, cells));
-    return (ctx->evap ? si.et_name : si.name) + targs;
+    return (ctx->days ? si.day_name : ctx->evap ? si.et_name : si.name) + targs;
   };
   return kind == K_MIXED ? name(K_SOLO) + "+" + name(K_PAIR) : name(kind);
 }
@@ -210,6 +210,9 @@ void h9g_destroy(h9g_ctx *ctx) {
   (void)hipFree(ctx->d_mon);
   (void)hipFree(ctx->d_mon_s);
   (void)hipFree(ctx->d_mon_ret);
+  (void)hipFree(ctx->d_day);
+  (void)hipFree(ctx->d_day_s);
+  (void)hipFree(ctx->d_day_ret);
   (void)hipFree(ctx->d_hist);
   (void)hipFree(ctx->d_aqbits);
   (void)hipFree(ctx->d_pace);
@@ -662,20 +665,23 @@ static int year_ranges(const h9g_ctx *ctx, LaunchRange r[2]) {
 // kind's year, year_ranges' two launches (neither with a second group).
 // mon: the base of the launch's monthly rows; then the shape's monthly kernel.
 // An ET context (h9g_set_evap): the shape's ET kernel, with mon or without.
-static int launch_year(h9g_ctx *ctx, Shape shape, bool mixed, KArgs a, float *mon) {
+// day: the base of the launch's day rows (h9g_set_days); then the shape's day
+// kernel, with mon or without.
+static int launch_year(h9g_ctx *ctx, Shape shape, bool mixed, KArgs a, float *mon, float *day) {
   if (mixed) {
     LaunchRange r[2];
     const int nr = year_ranges(ctx, r);
     for (int i = 0; i < nr; i++) {
       a.c0 = r[i].c0;
       a.cend = a.bend = a.split = r[i].cend;
-      if (int rc = launch_year(ctx, r[i].shape, false, a, mon)) return rc;
+      if (int rc = launch_year(ctx, r[i].shape, false, a, mon, day)) return rc;
     }
     return 0;
   }
-  if (int rc = ctx->evap ? h9g_et_launch(shape, &ctx->cfg, ctx->sc, a, mon)
-               : mon     ? h9g_mon_launch(shape, &ctx->cfg, ctx->sc, a, mon)
-                         : h9g_plain_launch(shape, &ctx->cfg, ctx->sc, a))
+  if (int rc = day         ? h9g_day_launch(shape, &ctx->cfg, ctx->sc, a, mon, day)
+               : ctx->evap ? h9g_et_launch(shape, &ctx->cfg, ctx->sc, a, mon)
+               : mon       ? h9g_mon_launch(shape, &ctx->cfg, ctx->sc, a, mon)
+                           : h9g_plain_launch(shape, &ctx->cfg, ctx->sc, a))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -710,6 +716,8 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
   const bool mon = ctx->monthly && !ys.probe;   // (a probe never records months)
   if (mon && ((d_list && !ys.mon_dst) || (two && !ys.mon2))) return H9G_EINVAL;
+  const bool day = ctx->days && !ys.probe;      // (nor days: a probe runs on the ET kernels)
+  if (day && ((d_list && !ys.day_dst) || (two && !ys.day2))) return H9G_EINVAL;
 #if defined(H9G_DUMP_AQ)
   if (d_list || ys.st) return H9G_EINVAL;   // (the record is indexed by the annual array's cell)
 #endif
@@ -728,6 +736,17 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (mon && !ctx->d_mon) {                 // NaN until a year writes it, as d_ann
     HIPCHK(hipMalloc(&ctx->d_mon, sizeof(float) * mrows * ctx->n));
     HIPCHK(hipMemsetAsync(ctx->d_mon, 0xff, sizeof(float) * mrows * ctx->n, ctx->sc));
+  }
+  // the day rows: every day of the longest year, so that a year's rows lie
+  // at the same place whatever its length
+  const size_t drows = (size_t)ctx->cfg.max_days * H9G_NDAYREC;
+  if (day && !ctx->d_day) {                 // NaN until a year writes it, as d_mon
+    if (hipMalloc(&ctx->d_day, sizeof(float) * drows * ctx->n) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->d_day = nullptr;
+      return H9G_ENOMEM;
+    }
+    HIPCHK(hipMemsetAsync(ctx->d_day, 0xff, sizeof(float) * drows * ctx->n, ctx->sc));
   }
   KArgs a;
   a.ncell = n;
@@ -766,6 +785,11 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
     if (!ctx->d_forc_s) HIPCHK(hipMalloc(&ctx->d_forc_s, sizeof(float) * 7 * (size_t)ctx->cfg.max_days * ios));
     if (!ctx->d_ann_s) HIPCHK(hipMalloc(&ctx->d_ann_s, sizeof(float) * annual_rows(ctx->L) * ios));
     if (mon && !ctx->d_mon_s) HIPCHK(hipMalloc(&ctx->d_mon_s, sizeof(float) * mrows * ios));
+    if (day && !ctx->d_day_s && hipMalloc(&ctx->d_day_s, sizeof(float) * drows * ios) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->d_day_s = nullptr;
+      return H9G_ENOMEM;
+    }
   }
   const size_t dvar = (size_t)ctx->cfg.max_days * ios;
   // the second group from the first whole wave after the first group's
@@ -827,6 +851,8 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (a.sorted_io) a.fvar = dvar;
   // the monthly rows, addressed as a.annual
   float *const mon_a = !mon ? nullptr : a.sorted_io ? ctx->d_mon_s : ctx->d_mon;
+  // ... and the day rows
+  float *const day_a = !day ? nullptr : a.sorted_io ? ctx->d_day_s : ctx->d_day;
   // workgroups of the launch (the pair part's, for the mixed kind)
   const size_t blocks = shape_blocks(shape, kind == K_MIXED ? ctx->n - ctx->n_solo : (size_t)a.cend);
   if (si.pair) {
@@ -887,7 +913,7 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   ctx->ev_kind[e] = ys.probe ? K_PROBE : kind;
   ctx->ev_cells[e] = (int64_t)ncells + (two ? ys.k2 : 0);
   HIPCHK(hipEventRecord(ctx->ev0[e], ctx->sc));
-  if (int r = launch_year(ctx, shape, kind == K_MIXED, a, mon_a)) return r;
+  if (int r = launch_year(ctx, shape, kind == K_MIXED, a, mon_a, day_a)) return r;
   // a one-column context's name is the kernel its last year ran on (the
   // launch record of the shape; until a year runs, h9g_create's)
   if (kind == K_PAIR1 && ctx->kind == K_PAIR1) ctx->kname = year_kernel_name(ctx, kind, ncells);
@@ -907,6 +933,13 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
       if (two)
         h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
             ys.k2, n, (int)mrows, a.split, ios, a.perm, ctx->d_mon_s, ys.mon2);
+    }
+    if (day) {                          // each group the days of its own year
+      h9g_unperm_annual_kernel<<<dim3((unsigned)((ncells + 255) / 256), rows), 256, 0, ctx->sc>>>(
+          (int)ncells, n, nt * H9G_NDAYREC, 0, ios, a.perm, ctx->d_day_s, d_list ? ys.day_dst : ctx->d_day);
+      if (two)
+        h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
+            ys.k2, n, nt2 * H9G_NDAYREC, a.split, ios, a.perm, ctx->d_day_s, ys.day2);
     }
     HIPCHK(hipGetLastError());
   }
@@ -1062,10 +1095,15 @@ int h9g_run_year(h9g_ctx *ctx, int slot, int jyear) {
   ys.slot = slot;
   ys.jyear = jyear;
   if (ctx) ctx->mon_years = 0;
+  if (ctx) ctx->day_nt.clear();
   const int r = run_year_impl(ctx, ys);
   if (r == 0 && ctx->monthly) {
     ctx->mon_years = 1;
     ctx->mon_in_ret = false;
+  }
+  if (r == 0 && ctx->days) {
+    ctx->day_nt.assign(1, days_in_year(jyear));
+    ctx->day_in_ret = false;
   }
   return r;
 }
@@ -1091,6 +1129,7 @@ int h9g_set_evap(h9g_ctx *ctx, int on) {
 #if defined(H9G_STAMPS)
   if (on) return H9G_EINVAL;   // (as h9g_set_monthly)
 #endif
+  if (!on && ctx->days) return H9G_ESTATE;   // day recording rides on the ET sum (h9g_set_days)
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   if (ctx->evap != (on ? 1 : 0)) {
@@ -1112,6 +1151,56 @@ int h9g_get_monthly(h9g_ctx *ctx, int k, float *out) {
   const size_t year = (size_t)H9G_NMONTHS * annual_rows(ctx->L) * ctx->n;
   HIPCHK(hipMemcpy(out, ctx->mon_in_ret ? ctx->d_mon_ret + (size_t)k * year : ctx->d_mon, sizeof(float) * year,
                    hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Day records (include/h9g.h): needs ET recording on.  The context's name
+// follows (h9g_kernel_name: the day kernels').
+int h9g_set_days(h9g_ctx *ctx, int on) {
+  if (!ctx) return H9G_EINVAL;
+#if defined(H9G_STAMPS)
+  if (on) return H9G_EINVAL;   // (as h9g_set_monthly)
+#endif
+  if (on && !ctx->evap) return H9G_ESTATE;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  if (ctx->days != (on ? 1 : 0)) {
+    ctx->days = on ? 1 : 0;
+    const std::string from = on ? "_et_kernel" : "_day_kernel", to = on ? "_day_kernel" : "_et_kernel";
+    for (size_t p = 0; (p = ctx->kname.find(from, p)) != std::string::npos; p += to.size())
+      ctx->kname.replace(p, from.size(), to);
+  }
+  ctx->day_nt.clear();
+  return 0;
+}
+
+int h9g_get_days(h9g_ctx *ctx, int k, float *out) {
+  if (!ctx || !out) return H9G_EINVAL;
+  if (ctx->day_nt.empty()) return H9G_ESTATE;
+  if (k < 0 || (size_t)k >= ctx->day_nt.size()) return H9G_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  const size_t year = (size_t)ctx->cfg.max_days * H9G_NDAYREC * ctx->n;
+  HIPCHK(hipMemcpy(out, ctx->day_in_ret ? ctx->d_day_ret + (size_t)k * year : ctx->d_day,
+                   sizeof(float) * (size_t)ctx->day_nt[(size_t)k] * H9G_NDAYREC * ctx->n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Room for the day records of an ordered call's `nyears` years; none recorded yet.
+int day_begin(h9g_ctx *ctx, int nyears) {
+  ctx->day_nt.clear();
+  ctx->day_base = 0;
+  if (ctx->day_ret_cap >= (size_t)nyears) return 0;
+  HIPCHK(hipStreamSynchronize(ctx->sc));
+  (void)hipFree(ctx->d_day_ret);
+  ctx->d_day_ret = nullptr;
+  ctx->day_ret_cap = 0;
+  if (hipMalloc(&ctx->d_day_ret, sizeof(float) * (size_t)nyears * ctx->cfg.max_days * H9G_NDAYREC * ctx->n) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return H9G_ENOMEM;
+  }
+  ctx->day_ret_cap = (size_t)nyears;
   return 0;
 }
 

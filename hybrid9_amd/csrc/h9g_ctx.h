@@ -3,7 +3,7 @@
 // Included by h9g.hip (context, forcing, the year launch, recording),
 // h9g_ord.hip (the ordered mode), h9g_spin.hip (spin-up) and h9g_aux.hip (soil
 // build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
-// h9g_et.hip, h9g_cols.hip) do not include it: a change here recompiles no
+// h9g_et.hip, h9g_day.hip, h9g_cols.hip) do not include it: a change here recompiles no
 // geometry-templated kernel.  Their launchers are declared in h9g_year.h.
 #pragma once
 #include <stdint.h>
@@ -114,6 +114,16 @@ struct h9g_ctx {
   // evapotranspiration output (h9g_set_evap; the ET kernels): row evap of the
   // annual and monthly rows is the year's evaporation sum.  No buffer of its own.
   int evap = 0;
+  // day records (h9g_set_days / h9g_get_days; the day kernels): a year's
+  // H9G_NDAYREC values per cell and day
+  int days = 0;                   // recording on (then evap is on)
+  float *d_day = nullptr;         // a year's records, max_days x 7 rows of n (as d_ann)
+  float *d_day_s = nullptr;       // ... in slot order (as d_ann_s)
+  float *d_day_ret = nullptr;     // an ordered call's years, (years, max_days, 7, n)
+  size_t day_ret_cap = 0;         // years allocated there
+  int day_base = 0;               // first year of the running ordered call there
+  std::vector<int> day_nt;        // days of each year recorded by the last call (empty: none)
+  bool day_in_ret = false;        // ... in d_day_ret (an ordered call) or d_day (h9g_run_year)
   struct SpinBufs *spin = nullptr;   // h9g_spinup's buffers (h9g_spin.hip); null until its first call
 };
 
@@ -124,6 +134,7 @@ struct YearSpec {
   int m = 0;
   float *ann_dst = nullptr;      // list launches: their annual means into these rows (stride n, cell order)
   float *mon_dst = nullptr;      // ... and, with monthly recording on, their month-end snapshots into these
+  float *day_dst = nullptr;      // ... and, with day recording on, their day records into these (max_days x 7 rows)
   float *st = nullptr;           // the cells' state and STOP rows (null: the context's own)
   int *err = nullptr;
   bool bulk = false;             // a list launch that is a year of the context's cells (h9g_run_ordered's
@@ -136,6 +147,7 @@ struct YearSpec {
   const int *h2 = nullptr;
   int k2 = 0, slot2 = 0, jyear2 = 0;
   float *st2 = nullptr, *ann2 = nullptr, *mon2 = nullptr;   // (mon2: with monthly recording on)
+  float *day2 = nullptr;                                    // (with day recording on)
   int *err2 = nullptr;
   // list launches: only the year's first `ndays` days (0: all), the annual
   // rows as undivided running sums (the cell order's day-1 probe)
@@ -155,6 +167,7 @@ H9G_LOCAL int daily_begin(h9g_ctx *ctx, int jyear0, int nyears);
 H9G_LOCAL int daily_launch(h9g_ctx *ctx, const float *st, const float *guess, const int *err, const int32_t *slots,
                            int jyear0, int ny);
 H9G_LOCAL int mon_begin(h9g_ctx *ctx, int nyears);
+H9G_LOCAL int day_begin(h9g_ctx *ctx, int nyears);
 H9G_LOCAL int diag_launch(h9g_ctx *ctx);
 // h9g_ord.hip
 H9G_LOCAL void ord_free(h9g_ctx *ctx);

@@ -848,6 +848,66 @@ int h9g_write_mxy_nc_evap(const char *path, int nx, int ny, int nlayers, const f
   return write_mxy(path, nx, ny, nlayers, zc, ncell, gid, jyear, nisurf, snapshots, true);
 }
 
+// dxyYYYY.nc: one year of day records (h9g_get_days: (nday, 7, ncell)) of the
+// cells `gid` under a leading dimension time, on axyYYYY.nc's grid.  Runoff
+// and evapotranspiration are the day's amounts, derived from the year's
+// running sums in double, (double)S[d] - (double)S[d-1] with S[-1] = 0,
+// rounded to float; the other rows are written as recorded.  Written variable
+// by variable (write_cdf2): the largest host buffer is one variable's.
+int h9g_write_dxy_nc(const char *path, int nx, int ny, int nlayers, const float *zc, int ncell, const int64_t *gid,
+                     int jyear, int nday, const float *records) {
+  const bool leap = jyear % 4 == 0 && (jyear % 100 != 0 || jyear % 400 == 0);   // INIT.f90:844-859
+  if (!path || nx <= 0 || ny <= 0 || nlayers < 1 || nlayers > H9G_LMAX || ncell < 0 || nday < 1 ||
+      nday > (leap ? 366 : 365) || (ncell && (!gid || !records)))
+    return H9G_EINVAL;
+  for (int c = 0; c < ncell; c++)
+    if (gid[c] < 0 || gid[c] >= (int64_t)nx * ny) return H9G_EINVAL;
+  const float nan = std::nanf("");
+  const std::vector<std::pair<std::string, uint32_t>> dims = {{"time", (uint32_t)nday},
+                                                              {"latitude", (uint32_t)ny},
+                                                              {"longitude", (uint32_t)nx},
+                                                              {"layer_centre_depth", (uint32_t)nlayers}};
+  struct F2 { const char *name, *units; int row; bool diff; };
+  const F2 f2[H9G_NDAYREC] = {{"runoff", "mm/day", 0, true},
+                              {"evapotranspiration", "mm/day", 1, true},
+                              {"soil_water", "mm", 2, false},
+                              {"soil_water_top_layer", "mm^3/mm^3", 3, false},
+                              {"water_table_depth", "mm", 4, false},
+                              {"aquifer_water", "mm", 5, false},
+                              {"LAI", "m^2/m^2", 6, false}};
+  const uint64_t plane = (uint64_t)nx * ny;
+  char since[64];
+  snprintf(since, sizeof(since), "days since %04d-01-01", jyear);
+  std::vector<WVar> vars;
+  vars.push_back({"time", {0}, {text_att("units", since)}, (uint64_t)nday});
+  vars.push_back({"latitude", {1}, {text_att("units", "degrees_north")}, (uint64_t)ny});
+  vars.push_back({"longitude", {2}, {text_att("units", "degrees_east")}, (uint64_t)nx});
+  vars.push_back({"layer_centre_depth", {3}, {text_att("units", "mm")}, (uint64_t)nlayers});
+  for (const F2 &v : f2)
+    vars.push_back({v.name, {0, 1, 2}, {text_att("units", v.units), float_att("_FillValue", nan)}, plane * nday});
+  const float dlon = 360.0f / (float)nx, dlat = 180.0f / (float)ny;
+  return write_cdf2(path, dims, vars, [&](size_t k, float *out) {
+    if (k == 0) {
+      for (int d = 0; d < nday; d++) out[d] = (float)d;
+    } else if (k == 1) {                         // as write_xy_nc
+      for (int y = 0; y < ny; y++) out[y] = (90.0f - 0.5f * dlat) - (float)y * dlat;
+    } else if (k == 2) {
+      for (int x = 0; x < nx; x++) out[x] = (-180.0f + 0.5f * dlon) + (float)x * dlon;
+    } else if (k == 3) {
+      for (int i = 0; i < nlayers; i++) out[i] = zc ? zc[i] : nan;
+    } else {
+      const F2 &v = f2[k - 4];
+      for (uint64_t i = 0; i < plane * nday; i++) out[i] = nan;
+      for (int d = 0; d < nday; d++) {
+        const float *s1 = records + ((size_t)d * H9G_NDAYREC + v.row) * ncell;
+        const float *s0 = d ? s1 - (size_t)H9G_NDAYREC * ncell : nullptr;
+        for (int c = 0; c < ncell; c++)
+          out[(uint64_t)d * plane + gid[c]] = v.diff ? (float)((double)s1[c] - (s0 ? (double)s0[c] : 0.0)) : s1[c];
+      }
+    }
+  });
+}
+
 // READ_PGF.f90 + READ_NET_CDF_3DR.f90 for the cells of a context: days
 // [t0, t0+nt) of the 7 files (READ_PGF order tas rlds rsds huss ps pr rhs),
 // variable 4 of each (dims time, lat, lon), gathered at the grid ids gid

@@ -207,6 +207,8 @@ struct OrdDec {
   float *st0 = nullptr, *guess = nullptr, *ann = nullptr, *ck = nullptr;
   float *mon = nullptr;                  // monthly recording: the snapshots beside ann, (years, 12, annual rows, n)
   int mon_cap = 0;                       // years allocated there
+  float *day = nullptr;                  // day recording: the day records beside ann, (years, max_days, 7, n)
+  int day_cap = 0;                       // years allocated there
   int *err0 = nullptr, *eck = nullptr, *dirty = nullptr;
   int *d_chain = nullptr, *d_pred = nullptr, *d_first = nullptr, *d_list = nullptr, *d_flag = nullptr;
   std::vector<int> chain, list, flag;
@@ -231,7 +233,7 @@ void ord_free(h9g_ctx *ctx) {
   OrdBufs *o = ctx->ord;
   if (!o) return;
   for (OrdDec &D : o->d) {
-    for (float *p : {D.st0, D.guess, D.ann, D.ck, D.mon}) (void)hipFree(p);
+    for (float *p : {D.st0, D.guess, D.ann, D.ck, D.mon, D.day}) (void)hipFree(p);
     for (int *p : {D.err0, D.eck, D.dirty, D.d_chain, D.d_pred, D.d_first, D.d_list, D.d_flag}) (void)hipFree(p);
   }
   (void)hipFree(o->st2);
@@ -306,6 +308,26 @@ static int ord_mon_alloc(h9g_ctx *ctx, int ny) {
       return H9G_ENOMEM;
     }
     D.mon_cap = ny;
+  }
+  return 0;
+}
+
+// The day rows of a decade's year (h9g_set_days), likewise.
+static size_t ord_day_year(const h9g_ctx *ctx) { return (size_t)ctx->cfg.max_days * H9G_NDAYREC * ctx->n; }
+static float *ord_day(const h9g_ctx *ctx, const OrdDec &D, int y) {
+  return ctx->days ? D.day + (size_t)y * ord_day_year(ctx) : nullptr;
+}
+static int ord_day_alloc(h9g_ctx *ctx, int ny) {
+  for (OrdDec &D : ctx->ord->d) {
+    if (D.day && D.day_cap >= ny) continue;
+    (void)hipFree(D.day);
+    D.day = nullptr;
+    D.day_cap = 0;
+    if (hipMalloc(&D.day, sizeof(float) * (size_t)ny * ord_day_year(ctx)) != hipSuccess) {
+      (void)hipGetLastError();
+      return H9G_ENOMEM;
+    }
+    D.day_cap = ny;
   }
   return 0;
 }
@@ -481,6 +503,7 @@ static int ord_run_alone(h9g_ctx *ctx, OrdDec &D, const int32_t *slots, OrdStats
   ys.m = (int)D.list.size();
   ys.ann_dst = ord_ann(ctx, D, D.next_y);
   ys.mon_dst = ord_mon(ctx, D, D.next_y);
+  ys.day_dst = ord_day(ctx, D, D.next_y);
   ys.st = ctx->ord->st2;
   ys.err = ctx->ord->err2;
   if (int r = run_year_impl(ctx, ys)) return r;
@@ -534,6 +557,9 @@ static int ord_finish(h9g_ctx *ctx, OrdDec &D, OrdDec *N, float *annual, int &st
   if (ctx->monthly)       // the settled decade's months into the call's retained buffer
     HIPCHK(hipMemcpyAsync(ctx->d_mon_ret + (size_t)(ctx->mon_base + D.k0) * H9G_NMONTHS * rows * n, D.mon,
                           sizeof(float) * (size_t)D.ny * H9G_NMONTHS * rows * n, hipMemcpyDeviceToDevice, ctx->sc));
+  if (ctx->days)          // ... and its day records
+    HIPCHK(hipMemcpyAsync(ctx->d_day_ret + (size_t)(ctx->day_base + D.k0) * ord_day_year(ctx), D.day,
+                          sizeof(float) * (size_t)D.ny * ord_day_year(ctx), hipMemcpyDeviceToDevice, ctx->sc));
   if (N) {
     h9g_settle_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->sc>>>(
         (int)n, srows, rows, N->ny, ord_ck(ctx, D, D.ny - 1), ord_eck(ctx, D, D.ny - 1), N->st0, N->err0, N->dirty,
@@ -541,6 +567,7 @@ static int ord_finish(h9g_ctx *ctx, OrdDec &D, OrdDec *N, float *annual, int &st
     // NaN months where it wrote NaN means: a cell that starts N stopped runs
     // none of N's years (N's first pass is done, and its chains leave it out)
     if (ctx->monthly) h9g_mon_stopped((int)n, N->ny * H9G_NMONTHS * rows, N->err0, N->mon, ctx->sc);
+    if (ctx->days) h9g_mon_stopped((int)n, N->ny * ctx->cfg.max_days * H9G_NDAYREC, N->err0, N->day, ctx->sc);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(ctx->sc));
@@ -588,6 +615,8 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
   if (int r = ord_alloc(ctx, nymax)) return r;
   if (ctx->monthly)
     if (int r = ord_mon_alloc(ctx, nymax)) return r;
+  if (ctx->days)
+    if (int r = ord_day_alloc(ctx, nymax)) return r;
   OrdBufs *o = ctx->ord;
   // land cells (HYBRID9.f90:122-123, summed in layer order as the year
   // kernels do)
@@ -657,6 +686,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
         ys.bulk = true;
         ys.ann_dst = ctx->d_ann;
         ys.mon_dst = ctx->d_mon;
+        ys.day_dst = ctx->d_day;
       }
       const bool ride = P && P->phase == OrdDec::RERUN && g2_fits(ctx, (size_t)nb, P->list.size()) &&
                         !ctx->no_ride;
@@ -669,6 +699,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
         ys.err2 = o->err2;
         ys.ann2 = ord_ann(ctx, *P, P->next_y);
         ys.mon2 = ord_mon(ctx, *P, P->next_y);
+        ys.day2 = ord_day(ctx, *P, P->next_y);
       }
       if (int r = run_year_impl(ctx, ys)) return r;
       S.ticks++;
@@ -676,6 +707,9 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
       if (ctx->monthly)
         HIPCHK(hipMemcpyAsync(ord_mon(ctx, D, y), ctx->d_mon, sizeof(float) * H9G_NMONTHS * rows * n,
                               hipMemcpyDeviceToDevice, ctx->sc));
+      if (ctx->days)
+        HIPCHK(hipMemcpyAsync(ord_day(ctx, D, y), ctx->d_day, sizeof(float) * ord_day_year(ctx), hipMemcpyDeviceToDevice,
+                              ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_ck(ctx, D, y), ctx->d_st, sizeof(float) * srows * n, hipMemcpyDeviceToDevice, ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_eck(ctx, D, y), ctx->d_err, sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToDevice, ctx->sc));
       if (ride) {
@@ -743,6 +777,11 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
     ctx->mon_years = ctx->mon_base + nyears;
     ctx->mon_in_ret = true;
   }
+  if (ctx->days) {
+    ctx->day_nt.resize((size_t)ctx->day_base);
+    for (int y = 0; y < nyears; y++) ctx->day_nt.push_back(days_in_year(jyear0 + y));
+    ctx->day_in_ret = true;
+  }
   // the first STOP of the call (h9g_last_error) or one from before it
   return h9g_sync(ctx);
 }
@@ -769,6 +808,8 @@ int h9g_run_decade_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int n
   }
   if (ctx && ctx->monthly)
     if (int r = mon_begin(ctx, nyears)) return r;
+  if (ctx && ctx->days)
+    if (int r = day_begin(ctx, nyears)) return r;
   return run_ordered_impl(ctx, slots, jyear0, {{jyear0, nyears}}, annual, passes);
 }
 
@@ -776,6 +817,8 @@ int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, 
   if (nyears < 1 || jyear0 < 1861) return H9G_EINVAL;
   if (ctx && ctx->monthly)
     if (int r = mon_begin(ctx, nyears)) return r;
+  if (ctx && ctx->days)
+    if (int r = day_begin(ctx, nyears)) return r;
   if (ctx && !ctx->daily_sel.empty()) {
     // with a selection the decades run one after another, each as
     // h9g_run_decade_ordered runs it (the same results bit for bit), and each
@@ -790,6 +833,7 @@ int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, 
     int first = 0, k0 = 0, i = 0;
     for (const auto &d : ref_decades(jyear0, nyears)) {
       ctx->mon_base = k0;
+      ctx->day_base = k0;
       const int r = run_ordered_impl(ctx, slots + k0, d.first, {d}, annual ? annual + (size_t)k0 * rows * ctx->n : nullptr,
                                      passes ? passes + i : nullptr);
       if (r < 0) return r;

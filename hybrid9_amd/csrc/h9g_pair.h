@@ -2397,6 +2397,56 @@ struct MonthsEt {
   }
 };
 
+// DaysEt: the day kernels' (h9g_set_days; DESIGN.md §7 "Day records"), with
+// EvapProf.  Its month-end part is MonthsEt's (M0 may be null).  Its day part:
+// the H9G_NDAYREC values a day leaves -- after the day's last substep, GROW
+// and the day's additions -- into the cell's day rows, value r of day d at
+// D[(d * 7 + r) * stride]: rnf_sum and evap_sum as they stand (cumulative and
+// never reset, as the month-end snapshots), the column's liquid water
+// h2osoi_liq(1) + ... + h2osoi_liq(L) added in that order, the day's addend to
+// theta_sum(1) (HYDROLOGY.f90:1233), zwt, wa and the LAI GROW left.  D0 may be
+// null (the cell order's day-1 probes): nothing is stored then, by a
+// wave-uniform test.  stop(): the days a cell that reaches a STOP on day
+// `day` does not complete are NaN -- the year's buffer is reused from year to
+// year, so the cell's earlier values there must go.
+// M0, D0 and A0 are the launch's bases of the monthly, day and annual rows,
+// the same for every lane: the cell's own rows lie as far from M0 and D0 as
+// its annual rows A from A0, and that offset is taken from A at the day's end,
+// so that no per-lane pointer of the policy's is live over the substep loop.
+struct DaysEt {
+  gbl_float *M0;
+  size_t stride;
+  gbl_float *D0;
+  const gbl_float *A0;
+  enum { NREC = 7 };
+  template <int L>
+  H9K_HD void day_end(int day, int nt, const gbl_float *A, size_t as, float rnf_sum, float evap_sum,
+                      const St<L> &s, float theta1) const {
+    if (D0) {
+      float w = s.h2o[1];
+#pragma unroll
+      for (int i = 2; i <= L; i++) w = w + s.h2o[i];
+      gbl_float *o = D0 + (A - A0) + (size_t)day * NREC * stride;
+      o[0] = rnf_sum;
+      o[stride] = evap_sum;
+      o[2 * stride] = w;
+      o[3 * stride] = theta1;
+      o[4 * stride] = s.zwt;
+      o[5 * stride] = s.wa;
+      o[6 * stride] = s.LAI;
+    }
+    MonthsEt{M0 ? M0 + (A - A0) : nullptr, stride}.template day_end<L>(day, nt, A, as, rnf_sum, evap_sum);
+  }
+  H9K_HD void stop(int day, int nt, const gbl_float *A) const {
+    if (!D0) return;
+    gbl_float *o = D0 + (A - A0);
+    const float nan = __builtin_nanf("");
+    for (size_t k = (size_t)day * NREC; k < (size_t)nt * NREC; k++) o[k * stride] = nan;
+  }
+};
+template <class MO>
+constexpr bool kDays = std::is_same<MO, DaysEt>::value;
+
 // The one-column kernel's two waves per column (PairStore kFront; h9g.hip
 // h9g_pair1f_kernel: a workgroup is one column's main wave and front wave).
 //
@@ -2595,6 +2645,8 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
     }
     if (code) {
       if constexpr (CS::kFront) front_done(cs);
+      if constexpr (kDays<MO>)
+        if (act) mo.stop(day, nt, A);
       return code;
     }
     if (!act) continue;
@@ -2625,7 +2677,9 @@ H9K_HD int cell_year_pair(const G &g, CS cs, const SP &sp, St<L> &s, const gbl_f
 #pragma unroll
     for (int k = 0; k < 12 + L; k++)
       if (later(k)) A[k * as] = a[k];
-    if constexpr (kEvap<PR>)
+    if constexpr (kDays<MO>)
+      mo.template day_end<L>(day, nt, A, as, rnf_sum, pr.sum, s, MAXF(s.h2o[1], 1.0E-6f) / g.thk(1));
+    else if constexpr (kEvap<PR>)
       mo.template day_end<L>(day, nt, A, as, rnf_sum, pr.sum);
     else
       mo.template day_end<L>(day, nt, A, as, rnf_sum);

@@ -220,7 +220,7 @@ int h9g_spinup(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, const
     for (int y = 0; y < nyears; y++)
       if (slots[y] < 0 || slots[y] >= ctx->cfg.nslots || used[(size_t)slots[y]]++) return H9G_EINVAL;
   }
-  if (!ctx->daily_sel.empty() || ctx->monthly) return H9G_ESTATE;   // spin-up records nothing
+  if (!ctx->daily_sel.empty() || ctx->monthly || ctx->days) return H9G_ESTATE;   // spin-up records nothing
   if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
   for (int y = 0; y < nyears; y++) {
     if (const int prc = join_prefetch(ctx, slots[y])) return prc;

@@ -3,8 +3,9 @@
 // the kernel definitions, the launch's cases and the reported names are
 // made), the kernel kinds, the geometry dispatch and launch_shape.  Included
 // by h9g_plain.hip, which instantiates the plain kernels, by h9g_mon.hip,
-// which instantiates the monthly ones, and by h9g_et.hip, which instantiates
-// the evapotranspiration (ET) ones, so that the three compile side by side
+// which instantiates the monthly ones, by h9g_et.hip, which instantiates
+// the evapotranspiration (ET) ones, and by h9g_day.hip, which instantiates the
+// day-record ones, so that the four compile side by side
 // (hybrid9_amd/build.py), beside h9g_cols.hip with the other
 // geometry-templated kernels; tools/isa_unit.hip instantiates single kernels
 // for the ISA study.  At its end: the kernel units' launchers, which is all
@@ -108,6 +109,13 @@ template <int L>
 constexpr int pair_waves() { return pair_resident<L>(); }
 static_assert(pair_waves<8>() == pair_waves<10>(), "one row of the shape table serves both layer counts");
 
+// The day rows (h9g_set_days) of a cell that does not run its year: NaN on
+// each of its nt days, as nan_rows.
+static_assert(H9G_NDAYREC == DaysEt::NREC, "the day record of the ABI and of h9g_pair.h");
+__device__ __forceinline__ void nan_days(float *base, int nt, size_t n, int c) {
+  for (size_t r = 0; r < (size_t)nt * H9G_NDAYREC; r++) base[r * n + c] = __builtin_nanf("");
+}
+
 // ---------------------------------------------------------------------------
 // kernel kinds and launch shapes
 // ---------------------------------------------------------------------------
@@ -128,7 +136,7 @@ enum Kind : int {
 // Launch shapes: what a year launch actually runs on, one row per year kernel.
 //   X(id, stem, kind, threads, blocks, cols, waves, pair, g2)
 // stem: the kernel is h9g_<stem>_kernel, its monthly sibling h9g_<stem>_mon_kernel,
-// its ET sibling h9g_<stem>_et_kernel;
+// its ET sibling h9g_<stem>_et_kernel, its day sibling h9g_<stem>_day_kernel;
 // kind: the statistics row it counts under; threads per workgroup; column
 // blocks per workgroup; columns per wave (per column block); waves per SIMD =
 // workgroups resident per CU (the Pacer's round, pace_mode); pair: a pair
@@ -159,6 +167,7 @@ enum Shape : int { H9G_YEAR_SHAPES(H9G_SHAPE_ID) S_NSHAPE };
 struct ShapeInfo {
   const char *name;     // the kernel's name
   const char *et_name;  // its ET sibling's (what an ET context's years run on)
+  const char *day_name; // its day sibling's (what a context that records days runs them on)
   Kind kind;
   int threads, blocks, wave_cols, waves;
   bool pair, second_group;
@@ -168,7 +177,9 @@ struct ShapeInfo {
 constexpr ShapeInfo shape_info(Shape s) {
   switch (s) {
 #define H9G_SHAPE_ROW(id, stem, kind, threads, blocks, cols, waves, pair, g2) \
-  case id: return {"h9g_" #stem "_kernel", "h9g_" #stem "_et_kernel", kind, threads, blocks, cols, waves, pair, g2};
+  case id:                                                                     \
+    return {"h9g_" #stem "_kernel", "h9g_" #stem "_et_kernel", "h9g_" #stem "_day_kernel", kind, threads, blocks, cols, \
+            waves, pair, g2};
     H9G_YEAR_SHAPES(H9G_SHAPE_ROW)
 #undef H9G_SHAPE_ROW
     default: return {};
@@ -224,9 +235,14 @@ inline Shape year_shape(int kind, size_t cells) {
 // ET: the evapotranspiration kernels (cell_year_pair with EvapProf and
 // MonthsEt: row evap of the annual and monthly rows is the year's evaporation
 // sum); `mon` may be null there (no monthly recording), a wave-uniform test.
-template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT = false, bool ET = false>
-__device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr) {
+// DAY: the day kernels (h9g_set_days): the ET kernels with the DaysEt policy,
+// which stores the day records into `dayr`, addressed as a.annual
+// (H9G_NDAYREC rows per day); `dayr` may be null (a day-1 probe).
+template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT = false, bool ET = false,
+          bool DAY = false>
+__device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr, float *dayr = nullptr) {
   static_assert(!(MON && ET), "the ET kernels record months themselves");
+  static_assert(!DAY || ET, "the day kernels are ET kernels");
   typedef PairStore<L, 2 * C, R, FRONT ? 1 : 0> PS;
   static_assert(!FRONT || C == 1, "the front wave serves a one-column wave");
   constexpr int NW = FRONT ? 1 : H9G_PWAVES;               // column blocks per workgroup
@@ -318,6 +334,8 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
         if (h == 0 && !front_wave) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
       if constexpr (ET)
         if (mon && h == 0 && !front_wave) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);
+      if constexpr (DAY)
+        if (dayr && h == 0 && !front_wave) nan_days(dayr, nt, ios, io);
       return;
     }
     cell_inv_pair<L, G>(g, cs);
@@ -347,7 +365,12 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
     for (int k = 0; k < 8; k++) a.stamps[(blockIdx.x * NW + wave) * 8 + k] = pr.acc[k];
 #else
   int code;
-  if constexpr (ET)
+  if constexpr (DAY)
+    code = cell_year_pair<L, G, Split2, PS, true, EvapProf, DaysEt>(
+        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf, a.grow_on,
+        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, EvapProf{zero, g.dt()},
+        DaysEt{(gbl_float *)mon, ios, (gbl_float *)dayr, (const gbl_float *)a.annual});
+  else if constexpr (ET)
     code = cell_year_pair<L, G, Split2, PS, true, EvapProf, MonthsEt>(
         g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, nt, a.nisurf, a.grow_on,
         (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, EvapProf{zero, g.dt()},
@@ -385,6 +408,9 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
 // And each with its ET sibling (h9g_set_evap), the same way: EvapProf and
 // MonthsEt, `mon` null without monthly recording.  An ET context runs every
 // year launch on them, its day-1 probes included.
+// And each with its day sibling (h9g_set_days): EvapProf and DaysEt, the base
+// of the day rows an argument after `mon`.  A context that records days runs
+// its years on them; its day-1 probes stay on the ET kernels.
 //   * pair2: the pair kernel built for 2 waves per SIMD (round 4, VERDICT r03
 //     #2/#4): 256 VGPRs, so the L = 10 substep does not spill (the 3-wave build
 //     spills 108 VGPRs and 118 SGPRs into a 296-B-per-lane scratch that reaches
@@ -428,6 +454,11 @@ __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon
   __global__ void H9G_YEAR_ATTRS(id) h9g_##stem##_et_kernel(const KArgs a, float *mon, const G g) {              \
     pair_body<L, G, shape_info(id).waves, shape_info(id).wave_cols, false, shape_info(id).front(), true>(a, g,   \
                                                                                                         mon);   \
+  }                                                                                                              \
+  template <int L, class G>                                                                                      \
+  __global__ void H9G_YEAR_ATTRS(id) h9g_##stem##_day_kernel(const KArgs a, float *mon, float *day, const G g) { \
+    pair_body<L, G, shape_info(id).waves, shape_info(id).wave_cols, false, shape_info(id).front(), true, true>(  \
+        a, g, mon, day);                                                                                         \
   }
 H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
 #undef H9G_PAIR_KERNELS
@@ -439,8 +470,9 @@ H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
 // sibling (MON, `mon`: pair_body's): as an inlined function the same
 // statements compiled to other machine code for the kernel (blockDim.x loaded
 // from the dispatch packet; as with the row macros of h9g_rows.h).  ET: the
-// ET sibling (pair_body's; its store has the snapshot field SV_EVAP).
-#define H9G_SOLO_BODY(MON, ET, mon)                                                                                \
+// ET sibling (pair_body's; its store has the snapshot field SV_EVAP).  DAY,
+// dayr: the day sibling (pair_body's).
+#define H9G_SOLO_BODY(MON, ET, mon, DAY, dayr)                                                                     \
   typedef SoloStore<L, ET> SS;                                                                                     \
   __shared__ uint64_t s_e2[32];                                                                                    \
   __shared__ double s_l2[32];                                                                                      \
@@ -467,13 +499,20 @@ H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
     if constexpr (MON) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);                                      \
     if constexpr (ET)                                                                                              \
       if (mon) nan_rows(mon, H9G_NMONTHS * Rows<L>::ANNUAL, ios, io);                                              \
+    if constexpr (DAY)                                                                                             \
+      if (dayr) nan_days(dayr, a.nt, ios, io);                                                                     \
     return;                                                                                                        \
   }                                                                                                                \
   cell_inv_pair<L, G>(g, cs);                                                                                      \
   int eday = 0, estep = 0;                                                                                         \
   float errval = 0.0f;                                                                                             \
   int code;                                                                                                        \
-  if constexpr (ET)                                                                                                \
+  if constexpr (DAY)                                                                                               \
+    code = cell_year_pair<L, G, SplitAll, SS, false, EvapProf, DaysEt>(                                            \
+        g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, a.nt, a.nisurf, a.grow_on,                    \
+        (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, EvapProf{zero, g.dt()},                  \
+        DaysEt{(gbl_float *)mon, ios, (gbl_float *)dayr, (const gbl_float *)a.annual});                            \
+  else if constexpr (ET)                                                                                           \
     code = cell_year_pair<L, G, SplitAll, SS, false, EvapProf, MonthsEt>(                                          \
         g, cs, sp, s, (const gbl_float *)(a.forc + io), ios, a.fvar, a.nt, a.nisurf, a.grow_on,                    \
         (gbl_float *)(a.annual + io), ios, eday, estep, errval, T, a.raw, EvapProf{zero, g.dt()},                  \
@@ -503,15 +542,19 @@ H9G_PAIR_SHAPES(H9G_PAIR_KERNELS)
 
 template <int L, class G>
 __global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_kernel(const KArgs a, const G g) {
-  H9G_SOLO_BODY(false, false, ((float *)nullptr))
+  H9G_SOLO_BODY(false, false, ((float *)nullptr), false, ((float *)nullptr))
 }
 template <int L, class G>
 __global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_mon_kernel(const KArgs a, float *mon, const G g) {
-  H9G_SOLO_BODY(true, false, mon)
+  H9G_SOLO_BODY(true, false, mon, false, ((float *)nullptr))
 }
 template <int L, class G>
 __global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_et_kernel(const KArgs a, float *mon, const G g) {
-  H9G_SOLO_BODY(false, true, mon)
+  H9G_SOLO_BODY(false, true, mon, false, ((float *)nullptr))
+}
+template <int L, class G>
+__global__ void H9G_YEAR_ATTRS(S_SOLO) h9g_solo_day_kernel(const KArgs a, float *mon, float *day, const G g) {
+  H9G_SOLO_BODY(false, true, mon, true, day)
 }
 
 // ---------------------------------------------------------------------------
@@ -558,19 +601,23 @@ int geo_dispatch(const h9g_config &cfg, F &&f) {
 
 // The year kernel of `shape` -- V_MON: its monthly sibling, with `mon` the
 // base of the launch's monthly rows; V_ET: its ET sibling, `mon` the same or
-// null -- over a's slots [c0, cend), with the configuration's geometry
-// variant.  The plain case is h9g_plain_launch of h9g_plain.hip, the monthly
-// case h9g_mon_launch of h9g_mon.hip and the ET case h9g_et_launch of
-// h9g_et.hip, so each unit compiles only its own kernels.
-enum Variant : int { V_PLAIN = 0, V_MON, V_ET };
+// null; V_DAY: its day sibling, `mon` as V_ET's and `day` the base of the
+// launch's day rows -- over a's slots [c0, cend), with the configuration's
+// geometry variant.  The plain case is h9g_plain_launch of h9g_plain.hip, the
+// monthly case h9g_mon_launch of h9g_mon.hip, the ET case h9g_et_launch of
+// h9g_et.hip and the day case h9g_day_launch of h9g_day.hip, so each unit
+// compiles only its own kernels.
+enum Variant : int { V_PLAIN = 0, V_MON, V_ET, V_DAY };
 template <Variant V>
-int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const KArgs &a, float *mon) {
+int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const KArgs &a, float *mon,
+                 float *day = nullptr) {
   const unsigned grid = (unsigned)shape_blocks(shape, (size_t)(a.cend - a.c0)), block = (unsigned)shape_info(shape).threads;
   return geo_dispatch(cfg, [&](auto L, auto g) {
     switch (shape) {
 #define H9G_SHAPE_CASE(id, stem, ...)                                                              \
   case id:                                                                                         \
     if constexpr (!shape_at(id, L)) return (int)H9G_EINVAL;                                        \
+    else if constexpr (V == V_DAY) h9g_##stem##_day_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, mon, day, g); \
     else if constexpr (V == V_ET) h9g_##stem##_et_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, mon, g); \
     else if constexpr (V == V_MON) h9g_##stem##_mon_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, mon, g); \
     else h9g_##stem##_kernel<L, decltype(g)><<<grid, block, 0, stream>>>(a, g);                    \
@@ -587,10 +634,11 @@ int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const K
 // ---------------------------------------------------------------------------
 // h9g_plain.hip: launch_shape<V_PLAIN>.  h9g_mon.hip: launch_shape<V_MON>, and
 // the cell order's NaN rows of the cells that start a decade stopped.
-// h9g_et.hip: launch_shape<V_ET>.
+// h9g_et.hip: launch_shape<V_ET>.  h9g_day.hip: launch_shape<V_DAY>.
 int h9g_plain_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a);
 int h9g_mon_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
 int h9g_et_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
+int h9g_day_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon, float *day);
 int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);
 
 // Not exported from libh9g.so.

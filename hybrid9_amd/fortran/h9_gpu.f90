@@ -16,6 +16,7 @@ INTEGER, PARAMETER :: H9G_LMAX = 10
 INTEGER, PARAMETER :: H9G_NDIAG = 12
 INTEGER, PARAMETER :: H9G_NDAILY = 11
 INTEGER, PARAMETER :: H9G_NMONTHS = 12
+INTEGER, PARAMETER :: H9G_NDAYREC = 7
 INTEGER, PARAMETER :: H9G_ERR_TRIDIAG1 = 1, H9G_ERR_TRIDIAG2 = 2
 INTEGER, PARAMETER :: H9G_ERR_RSUB_POS = 3, H9G_ERR_IMBALANCE = 4
 INTEGER, PARAMETER :: H9G_ERR_NOSNAP = 5   ! internal invariant, not a reference STOP
@@ -422,6 +423,33 @@ INTERFACE
     TYPE(C_PTR), VALUE :: ctx
     INTEGER(C_INT), VALUE :: on
     INTEGER(C_INT) :: h9g_set_evap
+  END FUNCTION
+  ! Day records: on /= 0 makes later runs use the day year kernels, which
+  ! store 7 values per cell and day; needs h9g_set_evap on (H9G_ESTATE else).
+  FUNCTION h9g_set_days (ctx, on) BIND(C, NAME='h9g_set_days')
+    IMPORT :: C_PTR, C_INT
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: on
+    INTEGER(C_INT) :: h9g_set_days
+  END FUNCTION
+  ! The records of year k (0-based) of the last run: out (ncell, 7, nday_k).
+  FUNCTION h9g_get_days (ctx, k, out) BIND(C, NAME='h9g_get_days')
+    IMPORT :: C_PTR, C_INT, C_FLOAT
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: k
+    REAL(C_FLOAT) :: out (*)
+    INTEGER(C_INT) :: h9g_get_days
+  END FUNCTION
+  ! One year of day records (ncell, 7, nday) to dxyYYYY.nc: seven variables
+  ! under a leading dimension time, runoff and evapotranspiration per day.
+  FUNCTION h9g_write_dxy_nc (path, nx, ny, nlayers, zc, ncell, gid, jyear, nday, records) &
+      BIND(C, NAME='h9g_write_dxy_nc')
+    IMPORT :: C_INT, C_CHAR, C_FLOAT, C_INT64_T
+    CHARACTER(KIND=C_CHAR), INTENT(IN) :: path (*)
+    INTEGER(C_INT), VALUE :: nx, ny, nlayers, ncell, jyear, nday
+    REAL(C_FLOAT), INTENT(IN) :: zc (*), records (*)
+    INTEGER(C_INT64_T), INTENT(IN) :: gid (*)
+    INTEGER(C_INT) :: h9g_write_dxy_nc
   END FUNCTION
   FUNCTION h9g_last_kernel_ms (ctx) BIND(C, NAME='h9g_last_kernel_ms')
     IMPORT :: C_PTR, C_FLOAT

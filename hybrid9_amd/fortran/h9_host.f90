@@ -55,6 +55,13 @@ PROGRAM H9_HOST
 ! mxyYYYY.nc (then written by h9g_write_mxy_nc_evap) is the year's evaporation
 ! sum instead of the reference's zero, in both cell_order settings.
 !
+! days = 1 records every year kernel's day-end records (h9g_set_days,
+! DESIGN.md §7: runoff and ET sums, column water, top-layer water content,
+! water table, aquifer water and LAI of every cell on every day) and writes
+! each year's to <out_dir>/dxyYYYY.nc (h9g_write_dxy_nc), in both cell_order
+! settings and with or without monthly; it implies evap = 1.  The grid is
+! mxyYYYY.nc's.
+!
 ! spinup_cycles > 0 (0 = off, the default) spins the cold start of
 ! INIT.f90:707-811 up to equilibrium before the run proper (h9g_spinup,
 ! DESIGN.md §7): the run's first spinup_years years (default 1) are staged
@@ -91,13 +98,13 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 ! --- extension namelist ----------------------------------------------------
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
-INTEGER :: cell_order, ordered_decades, daily, monthly, evap
+INTEGER :: cell_order, ordered_decades, daily, monthly, evap, days
 INTEGER :: spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze
 REAL(C_DOUBLE) :: spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 INTEGER(C_INT64_T) :: seed
 NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
-                 cell_order, ordered_decades, daily, monthly, evap, &
+                 cell_order, ordered_decades, daily, monthly, evap, days, &
                  spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze, &
                  spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
@@ -135,6 +142,8 @@ INTEGER :: dfill, dnyr, udaily, ucsv, lon_s_w, lat_s_w, nwin, ix, iy
 REAL :: a_lon, b_lon, a_lat, b_lat, lon1, lat1
 ! --- monthly output (h9g_set_monthly): a year's snapshots and its grid ------
 REAL(C_FLOAT), ALLOCATABLE :: mon (:,:,:)
+! --- day records (h9g_set_days): a year's records, on the monthly output's grid
+REAL(C_FLOAT), ALLOCATABLE :: drec (:,:,:)
 INTEGER(C_INT64_T), ALLOCATABLE :: mgid (:)
 INTEGER :: mnx, mny
 ! --- spin-up (h9g_spinup) ---------------------------------------------------
@@ -149,7 +158,7 @@ REAL(C_DOUBLE), ALLOCATABLE :: shist (:,:)
 input_mode = 'synth'; case_dir = ''; out_dir = '.'; pgf_dir = '.'
 nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
-monthly = 0; evap = 0
+monthly = 0; evap = 0; days = 0
 spinup_cycles = 0; spinup_years = 1; spinup_min_cycles = 1; spinup_freeze = 1
 spinup_tol_water = HUGE (1.0D0); spinup_tol_zwt = HUGE (1.0D0); spinup_tol_plant = HUGE (1.0D0)
 daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
@@ -383,10 +392,18 @@ IF (daily /= 0) THEN
                   &  theta_ma_1,  lai,  lai_litter, w_i, fT'
   END IF
 END IF
+IF (days /= 0) evap = 1
 IF (evap /= 0) CALL chk (h9g_set_evap (ctx, 1))
 IF (monthly /= 0) THEN
   CALL chk (h9g_set_monthly (ctx, 1))
-  ALLOCATE (mon (ncell, 12 + L, H9G_NMONTHS), mgid (ncell))
+  ALLOCATE (mon (ncell, 12 + L, H9G_NMONTHS))
+END IF
+IF (days /= 0) THEN
+  CALL chk (h9g_set_days (ctx, 1))
+  ALLOCATE (drec (ncell, H9G_NDAYREC, 366))
+END IF
+IF (monthly /= 0 .OR. days /= 0) THEN
+  ALLOCATE (mgid (ncell))
   IF (TRIM (input_mode) == 'case') THEN
     mnx = ncell; mny = 1
     DO i = 1, ncell
@@ -438,6 +455,7 @@ IF (cell_order /= 0) THEN
       annual = annual_dec (:, :, k)
       CALL year_out (dsyr + k - 1)
       IF (monthly /= 0) CALL month_out (k - 1, dsyr + k - 1)
+      IF (days /= 0) CALL days_out (k - 1, dsyr + k - 1)
     END DO
     CALL h9g_check_stop (ctx, rc)
     WRITE (*,'(A,I5,A,I5,A,12I3)') ' years', dsyr, ' -', deyr, ' in cell order: passes per decade', &
@@ -456,6 +474,7 @@ DO iyr = 1, nyears
   CALL chk (h9g_get_annual (ctx, annual))
   CALL year_out (jyear)
   IF (monthly /= 0) CALL month_out (0, jyear)
+  IF (days /= 0) CALL days_out (0, jyear)
   IF (daily /= 0) THEN                       ! flushed at the end of each reference decade
     CALL daily_year (0, jyear)
     IF (MODULO (jyear - 1900, 10) == 0 .OR. iyr == nyears) CALL daily_flush ()
@@ -508,6 +527,18 @@ CONTAINS
                                   mgid, y, NISURF, mon))
     END IF
   END SUBROUTINE month_out
+
+  ! The day records of year k (0-based) of the last run, calendar year y, to
+  ! <out_dir>/dxyYYYY.nc.
+  SUBROUTINE days_out (k, y)
+    INTEGER, INTENT(IN) :: k, y
+    INTEGER :: n
+    n = time_BOY (y+1-1859) - time_BOY (y-1859)
+    CALL chk (h9g_get_days (ctx, k, drec))
+    WRITE (ydate,'(I4)') y
+    CALL chk (h9g_write_dxy_nc (TRIM (out_dir)//'/dxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, L, zc, ncell, &
+                                mgid, y, n, drec))
+  END SUBROUTINE days_out
 
   ! The daily lines of year k (0-based) of the last run, calendar year y,
   ! appended to the current decade's.

@@ -312,6 +312,60 @@ int h9g_get_monthly(h9g_ctx *ctx, int k, float *out);
  * context.  h9g_kernel_name then reports the ET kernel. */
 int h9g_set_evap(h9g_ctx *ctx, int on);
 
+/* --- day records: day-end records of every cell from the year kernels ---- */
+/* The daily line above is a shadow run of selected cells.  With day
+ * recording on, every year kernel stores H9G_NDAYREC floats for every cell
+ * and every day d = 0 .. nt-1 of the year, taken after the day's last
+ * substep, after GROW and after the additions of HYBRID9.f90:235-254 (where
+ * the month-end snapshots are taken):
+ *   row 0  rnf_sum: the year's running runoff sum as it stands (mm)
+ *   row 1  evap_sum: the year's running ET sum as it stands (mm; the ET
+ *          section's sum)
+ *   row 2  W = h2osoi_liq(1) + ... + h2osoi_liq(L), f32, added in that
+ *          order (mm)
+ *   row 3  theta(1) of HYDROLOGY.f90:1233, the day's addend to theta_sum(1)
+ *   row 4  zwt (mm)
+ *   row 5  wa (mm)
+ *   row 6  LAI after the day's GROW
+ * Rows 0 and 1 are cumulative, like the month-end snapshots and for the same
+ * reason: nothing is reset, every record is a prefix of the reference's own
+ * f32 summation and the year's sums stay the reference's.  The day's runoff
+ * and ET are derived on the host, in double: (double)S[d] - (double)S[d-1]
+ * with S[-1] = 0, in mm per day: deterministic, but derived, not reference
+ * quantities.  Row 0 and row 1 of a year's last day, divided by
+ * FLOAT(nt * NISURF), are rows rnf and evap of the annual means; at a month's
+ * last day they are rows rnf and evap of that month's snapshot.
+ * Day recording needs the ET sum, so it rides on ET recording:
+ * h9g_set_days(ctx, 1) returns H9G_ESTATE unless h9g_set_evap is on, and
+ * h9g_set_evap(ctx, 0) returns H9G_ESTATE while day recording is on.
+ * A cell that reaches a reference STOP on day e of a year keeps its records
+ * of days 0 .. e-1 of that year and has NaN from day e on and in every later
+ * year (the daily line's convention: the reference ends before the day
+ * completes); a masked cell, or one that had stopped before the year, has NaN
+ * throughout.
+ * The day kernels are the ET year kernels under other names
+ * (h9g_kernel_name reports them); with recording off (the default) not one
+ * launch, allocation or synchronisation is added, and with it on annual
+ * means, month-end snapshots, state, STOP records and daily lines are the
+ * bits of an ET run without it.  h9g_spinup records nothing: H9G_ESTATE with
+ * day recording on.  The records take max_days x 7 x ncell floats of device
+ * memory for a year in cell order and as much again in slot order (0.7 GB
+ * each for the 0.5 deg grid); an ordered call retains nyears x max_days x 7 x
+ * ncell floats and holds as much per decade in flight (the day rows live
+ * beside that year's annual rows, and the same launches write them: first
+ * passes, list re-runs, re-runs riding as a second group; the decades stay
+ * overlapped).  All of it is allocated by the run and released with the
+ * context (not part of h9g_config_bytes); H9G_ENOMEM if it does not fit.
+ * Day recording combines with monthly recording and with a daily selection
+ * wherever those two combine. */
+#define H9G_NDAYREC 7
+int h9g_set_days(h9g_ctx *ctx, int on);
+/* Day records of year k (0-based) of the last h9g_run_year (k = 0),
+ * h9g_run_decade_ordered or h9g_run_ordered call: out (nday_k, 7, ncell),
+ * cell fastest.  Synchronises.  H9G_ESTATE if nothing
+ * was recorded, H9G_EINVAL for a bad k. */
+int h9g_get_days(h9g_ctx *ctx, int k, float *out);
+
 /* --- spin-up to equilibrium: cycle a forcing period, retire settled cells - */
 /* The model cold-starts from INIT.f90:707-811, and the reference's only
  * answer is to repeat years (its LCLIM loop re-reads the site years
@@ -444,6 +498,16 @@ int h9g_write_mxy_nc(const char *path, int nx, int ny, int nlayers,
 int h9g_write_mxy_nc_evap(const char *path, int nx, int ny, int nlayers,
                           const float *zc, int ncell, const int64_t *gid,
                           int jyear, int nisurf, const float *snapshots);
+/* dxyYYYY.nc: one year of day records (h9g_get_days, (nday, 7, ncell)) of
+ * the cells gid under a leading dimension `time` of nday, with axyYYYY.nc's
+ * latitude / longitude schema and NaN _FillValue: runoff and
+ * evapotranspiration (mm/day: the day's amounts, derived from the running
+ * sums in double as described there), soil_water (mm), soil_water_top_layer
+ * (mm^3/mm^3), water_table_depth (mm), aquifer_water (mm) and LAI.  CDF-2,
+ * written variable by variable.  Host only. */
+int h9g_write_dxy_nc(const char *path, int nx, int ny, int nlayers,
+                     const float *zc, int ncell, const int64_t *gid, int jyear,
+                     int nday, const float *records);
 /* READ_PGF.f90 / READ_NET_CDF_3DR.f90: days [t0, t0+nt) of variable 4
  * (time, lat, lon) of the 7 PGF files (tas rlds rsds huss ps pr rhs)
  * gathered at the grid ids gid into out (7, nt, ncell).  Host only. */

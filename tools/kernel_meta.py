@@ -8,8 +8,8 @@ Extracts the .hip_fatbin section, unbundles the gfx950 code object with
 clang-offload-bundler and reads the AMDHSA metadata note with llvm-readelf:
 VGPRs, AGPRs, SGPRs, spilled VGPRs/SGPRs, private (scratch) bytes per lane
 and static LDS bytes per workgroup.  Without --all only the year kernels
-(pair, pair2, solo) and their monthly and ET siblings (*_mon_kernel,
-*_et_kernel, listed beside them) are printed."""
+(pair, pair2, solo) and their monthly, ET and day siblings (*_mon_kernel,
+*_et_kernel, *_day_kernel, listed beside them) are printed."""
 from __future__ import annotations
 
 import re
@@ -27,7 +27,7 @@ BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def code_objects(lib: Path, tmp: Path) -> list[Path]:
     """The gfx950 code object of every device translation unit of the library
-    (hybrid9_amd/build.py UNITS: the year kernels' three units, each with its
+    (hybrid9_amd/build.py UNITS: the year kernels' four units, each with its
     own instantiations of h9g_year.h's kernels, h9g_cols.hip and the host
     runtime's units with their small kernels), in link order: .hip_fatbin
     holds one offload bundle per unit, one after the other.  No caller may
@@ -101,7 +101,7 @@ def main() -> None:
     print(f"{'kernel':60s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'VGPR spill':>10s} {'SGPR spill':>10s} "
           f"{'private B':>9s} {'LDS B':>7s} {'code B':>7s}")
     for k, nm in sorted(zip(ks, names), key=lambda x: x[1]):
-        if "--all" not in sys.argv and not re.search(r"h9g_(pair|pair1|pair1f|pair2|pair11|solo)(_mon|_et)?_kernel", nm):
+        if "--all" not in sys.argv and not re.search(r"h9g_(pair|pair1|pair1f|pair2|pair11|solo)(_mon|_et|_day)?_kernel", nm):
             continue
         short = nm.replace("h9k::", "").replace("(KArgs, ", "(")
         print(f"{short[:60]:60s} {k.get('vgpr', 0):5d} {k.get('agpr', 0):5d} {k.get('sgpr', 0):5d} "
