@@ -1254,10 +1254,27 @@ static int stamps_report(h9g_ctx *ctx) {
       // main waves' (pair_body: one main wave per workgroup)
       std::vector<unsigned> fs(8 * nw);
       HIPCHK(hipMemcpy(fs.data(), ctx->d_stamps + 8 * ctx->stamp_blocks, sizeof(unsigned) * 8 * nw, hipMemcpyDeviceToHost));
-      double w = 0, f = 0;
-      for (size_t k = 0; k < nw; k++) { w += fs[8 * k]; f += fs[8 * k + 1]; }
-      fprintf(stderr, "h9g stamps, front waves (cycles/wave/substep): wait at barrier 1=%.0f front=%.0f\n", w / steps,
+      // Means over every substep, of both kinds together.  The labels hold for a
+      // substep that starts with the water table in the column: marks 3 and 4 of
+      // the chain call follow barrier 2, 5 and 6 are the chain, 7 the wait at
+      // barrier 3.  In a substep that starts below it the call returns before
+      // mark 3, so everything from the front's end to barrier 3 (the wait at
+      // barrier 2, the main wave's sweep and its own chain) falls into slot 7.
+      // So "chain" is the share of in-column substeps times the chain's length,
+      // and "wait at barrier 3" grows with the share of the other kind.
+      double w = 0, f = 0, w2 = 0, ch = 0, w3 = 0;
+      for (size_t k = 0; k < nw; k++) {
+        w += fs[8 * k];
+        f += fs[8 * k + 1];
+        w2 += fs[8 * k + 3] + fs[8 * k + 4];     // (H9G_P1_SIDE: the chain call's marks 3 and 4 follow barrier 2)
+        ch += fs[8 * k + 5] + fs[8 * k + 6];
+        w3 += fs[8 * k + 7];
+      }
+      fprintf(stderr, "h9g stamps, front waves (cycles/wave/substep): wait at barrier 1=%.0f front=%.0f", w / steps,
               f / steps);
+      if (ch > 0)                                // the water-table chain on the second wave
+        fprintf(stderr, " wait at barrier 2=%.0f chain=%.0f wait at barrier 3=%.0f", w2 / steps, ch / steps, w3 / steps);
+      fprintf(stderr, "\n");
     }
     // load balance: per-wave totals (the kernel lasts as long as its slowest wave)
     std::vector<double> wt(nw, 0.0);

@@ -100,7 +100,21 @@ static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_
 // energy balance, em1, infiltration), returning its results in FrontRes; or
 // everything but the front, which takes those results from the store's
 // hand-over rows behind a workgroup barrier.
-enum : int { ROLE_ALL = 0, ROLE_FRONT = 1, ROLE_MAIN = 2 };
+// Round 10, the two-wave shape's water-table chain (recharge through the zwt
+// clamps, HYDROLOGY.f90:856-1123): in a substep that starts with the water
+// table in the column it reads nothing the sweep produces, so the second wave
+// evaluates it too (ROLE_CHAIN, after its front) while the main wave
+// (ROLE_MAINS) sweeps, and hands the new zwt, wa, rsub_top, jwt and the
+// drainage loop's h2osoi_liq deltas over behind a third barrier
+// (front_year_pair).  H9G_P1_SIDE=0 builds round 9's two-wave kernel.
+#ifndef H9G_P1_SIDE
+#define H9G_P1_SIDE 1
+#endif
+#if !H9G_P1_FRONT || (H9G_P1_TASKS & 3) != 3   // the chain's operands are round A's and round C's
+#undef H9G_P1_SIDE
+#define H9G_P1_SIDE 0
+#endif
+enum : int { ROLE_ALL = 0, ROLE_FRONT = 1, ROLE_MAIN = 2, ROLE_CHAIN = 3, ROLE_MAINS = 4 };
 struct FrontRes {
   float qflx_surf, tran, evg, qflx_infl;
 };
@@ -327,11 +341,13 @@ constexpr int pair_resident() { return 3; }   // waves per SIMD (h9g.hip pair_wa
 // 256 VGPRs and 80 KB, so no spills and every reciprocal field; h9g.hip
 // h9g_pair2_kernel).
 // F = 1: the one-column kernel's two-wave shape (front_year_pair); its block
-// ends with the hand-over rows HO_*.
+// ends with the hand-over rows HO_*.  F = 2: that shape with the water-table
+// chain on the second wave (H9G_P1_SIDE), the rows HS_* after them.
 template <int L, int S, int R = pair_resident<L>(), int F = 0>
 struct PairStore {
   static constexpr int NT = L / 2;
   static constexpr bool kFront = F != 0;
+  static constexpr bool kSide = F == 2;         // ... whose second wave takes the water-table chain too
   static_assert(!kFront || S == 2, "the front wave serves a one-column wave");
   // LDS fields by layer count (3 workgroups per CU: at most 75 rows).  L = 8:
   // every reciprocal (75 rows).  L = 10 (5 rows per per-layer field): 1/(-psi)
@@ -360,7 +376,20 @@ struct PairStore {
     HO_SURF, HO_TRAN, HO_EVG, HO_INFL, HO_END
   };
   static_assert((HO_END - TH0 - L) % 2 == 0, "whole rows");
-  static constexpr int ROWS = NPF * NT + (NPS + 1) / 2 + (S == 2 ? NT : 0) + (kFront ? (HO_END - HO_SMP) / 2 : 0);
+  // The water-table chain's words (F = 2), after the front's: main -> second
+  // wave, wa written before barrier 1 and the rest before barrier 2 (the two
+  // single powers of round A, smp and zq of layer max(jwt, 1)); second wave ->
+  // main, written before barrier 3: zwt, wa, rsub_top, the final jwt, the
+  // exact-re-run flag, the STOP code and its value, and the layer and amount of
+  // up to two additions to h2osoi_liq (layer 0: none).
+  // tests/test_pair1_side_map.py restates the map.
+  enum : int {
+    HS_WA = HO_END, HS_P0, HS_PY, HS_RSMP, HS_RZQ, HS_PAD0,
+    HS_ZWT, HS_WAO, HS_RSUB, HS_JWT, HS_FLAG, HS_CODE, HS_ERRV, HS_I0, HS_R0, HS_I1, HS_R1, HS_PAD1, HS_END
+  };
+  static_assert((HS_END - HO_END) % 2 == 0, "whole rows");
+  static constexpr int ROWS =
+      NPF * NT + (NPS + 1) / 2 + (S == 2 ? NT : 0) + (kFront ? ((kSide ? HS_END : HO_END) - HO_SMP) / 2 : 0);
   static constexpr int GBLOCK = 65536;                      // bytes per workgroup (>= any LDS address)
   lds_float *self, *even;
   const lds_float *zt;                 // zi(0..L+1), then zi(0..L+1)/1000 (per block)
@@ -806,11 +835,41 @@ constexpr bool pair1_tasks() {
 // The end-of-step theta(1..L) of :1233 is left to the caller (end_theta).
 // ROLE (ROLE_*): the one-column kernel's two waves per column evaluate the
 // front (ROLE_FRONT, results into *fr) and the rest (ROLE_MAIN) of a substep
-// side by side; every other caller runs all of it.
+// side by side; every other caller runs all of it.  With the chain on the
+// second wave (H9G_P1_SIDE) the main wave is ROLE_MAINS: in a substep that
+// starts with the water table in the column it leaves the water-table chain
+// (pr.mark(4) to pr.mark(6)) to the second wave's ROLE_CHAIN call, which runs
+// that text alone on the handed-over operands, posts its results in place of
+// the h2osoi_liq additions and returns at pr.mark(6) (or with STOP 3); the
+// main wave takes them behind barrier 3 (front_year_pair has the protocol).
+template <class CS>
+constexpr int main_role() {
+  if constexpr (CS::kFront)
+    return CS::kSide ? ROLE_MAINS : ROLE_MAIN;
+  else
+    return ROLE_ALL;
+}
 template <int L, class G, class M, class SP, class CS, class PR = NoProf, int ROLE = ROLE_ALL>
 H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf_sum, float &errval,
                           M &m, PR &pr, FrontRes *fr = nullptr) {
   constexpr int NT = L / 2;
+  constexpr bool kMain = ROLE == ROLE_MAIN || ROLE == ROLE_MAINS;   // without the front
+  constexpr bool kChain = ROLE == ROLE_CHAIN;                       // the water-table chain alone
+  // A STOP of the main wave between barriers 2 and 3: the wave passes barrier 3
+  // on its way out, so its partner, which waits there in every substep, is
+  // released and both go on to the barrier 1 that ends the year (front_done).
+  // Premise: lanes 0 and 1 of the main wave take a STOP's branch together.
+  // They do, because both hold the whole column and evaluate the sweep, the
+  // pivots and bm(1) from the same exchanged operands (as every STOP of the
+  // two-barrier shape already assumed: cell_year_pair takes lane 0's code for
+  // the wave).  Lanes that parted here would pass one barrier more than the
+  // partner wave, which must not happen; a change that lets the two lanes'
+  // sweeps differ has to carry the code to the one barrier 3 below instead.
+#define STOP_RET(c)                                  \
+  {                                                  \
+    if constexpr (ROLE == ROLE_MAINS) cs.wg_sync();  \
+    return c;                                        \
+  }
   // At L = 10 the lane parity is made opaque here, so that values that
   // depend only on it -- a lane's geometry-table offsets of its own layers,
   // one per slot -- are recomputed inside the substep (an add each) instead
@@ -842,7 +901,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     // the front reads theta(1) alone: the same quotient with the same redo
     theta[1] = m.div_d(h2o[1], g.thk(1), g.rthk(1));
     m.div_fix(theta[1], h2o[1], g.thk(1));
-  } else {
+  } else if constexpr (!kChain) {
   w0 = DC(D_FORC) * dt + s.wa;
   bool bad = false;                      // deferred checks (MathFast::div_d)
 #pragma unroll
@@ -862,7 +921,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   const float fff = 1.0f / hkdepth;
   const float frac_h2osfc = zero;
   float qflx_surf = zero, tran = zero, evg = zero, qflx_infl = zero;
-  if constexpr (ROLE != ROLE_MAIN) {       // the front (ROLE_MAIN: from the front wave, below)
+  if constexpr (!kMain && !kChain) {       // the front (the main wave: from the front wave, below)
   const float qflx_top_soil = DC(D_FORC);
   const float fsat = cs.sc(PS_FMAX) * m.expf(-0.5f * fff * s.zwt);
   qflx_surf = fsat * qflx_top_soil;
@@ -1040,7 +1099,10 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   const int jwt = jwt_of<L>(s.zwt, zim);
   const bool aq = (jwt == L);
   cs.launder();
-  if constexpr (ROLE != ROLE_MAIN) pr.mark(1);
+  if constexpr (!kMain && !kChain) pr.mark(1);
+  if constexpr (kChain) {
+    if (aq) return 0;                      // a substep that starts below the column: the main wave's own
+  }
 
   // :517-567 equilibrium profile and :598-639 conductivity and matric
   // potential, own layers (independent phases)
@@ -1058,7 +1120,14 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   float c_q[L + 1], c_1[L + 1], c_2[L + 1];
   bool flux_done = false;
   float rc_smp = zero, rc_zq = zero;
-  {
+  if constexpr (kChain) {                  // the second wave: what the main wave posted before barrier 2
+    p0.v[0] = cs.ho(CS::HS_P0);
+    p1.v[0] = cs.ho(CS::HS_PY);
+    rc_smp = cs.ho(CS::HS_RSMP);
+    rc_zq = cs.ho(CS::HS_RZQ);
+    picks = false;
+    static_assert(!kChain || (kTask && (H9G_P1_TASKS & 2)), "the chain's operands come from the task rounds");
+  } else {
     float *const outq[1] = {zq};
     float *const outk[4] = {hk, dhkdw, smp, dsmpdw};
     // exact: the reference expression with every special case redone in place
@@ -1706,11 +1775,17 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   const float smp1 = eS.v[0], dsmpdw1 = eS.v[1];
   cs.launder();
   pr.mark(3);
-  if constexpr (ROLE == ROLE_MAIN) {
+  if constexpr (kMain) {
     // barrier 2 (front_year_pair): the front wave's results of this substep,
     // first read by the rows below.  Lanes 0 and 1 are here on every path (the
     // helper lanes have returned); every STOP of this function lies below.
     // Stamps: p1 is the wait here, the front wave's time that was not covered.
+    if constexpr (ROLE == ROLE_MAINS) {    // the chain's operands that only this wave holds
+      cs.set_ho(CS::HS_P0, p0.v[0]);
+      cs.set_ho(CS::HS_PY, p1.v[0]);
+      cs.set_ho(CS::HS_RSMP, rc_smp);
+      cs.set_ho(CS::HS_RZQ, rc_zq);
+    }
     cs.wg_sync();
     qflx_surf = cs.ho(CS::HO_SURF);
     tran = cs.ho(CS::HO_TRAN);
@@ -1767,8 +1842,9 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // raising the reference's STOPs.  Measured: 234.3 -> 230.1 ms (config 2);
   // keeping the layer arrays live for a whole-block redo instead spilled
   // 55 VGPRs and measured 238.9 ms.
-  bool tri_ok = false;
-  if constexpr (!M::kExact) {
+  bool tri_ok = kChain;                  // (the chain alone: no system)
+  if constexpr (kChain) dwat2[L + 1] = zero;
+  if constexpr (!M::kExact && !kChain) {
     bool bad = false, zp = false;
     float qo[L + 1], d1[L + 1], d2[L + 1];
     auto flux3_f = [&](float hki, float num, float dsi, float dsn, float dhk, float den, double rden, int k,
@@ -1863,7 +1939,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       BET = zero;
       zero_pivot = 0;
       const float bm1x = m.div(g.dz(1), dt, g.rdt()) + d1[1];
-      if (bm1x == 0.0f) { errval = bm1x; return 1; }                // :806-812
+      if (bm1x == 0.0f) { errval = bm1x; STOP_RET(1); }             // :806-812
       row(1, zero, bm1x, d2[1], qflx_infl - qo[1] - tran * ROOT(1));
 #pragma unroll
       for (int i = 2; i <= L - 1; i++)
@@ -1875,7 +1951,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
         row(L, -d1[L - 1], m.div(g.dz(L), dt, g.rdt()) - d2[L - 1] + d1[L], d2[L], qo[L - 1] - qo[L] - tran * ROOT(L));
         row(L + 1, -d1[L], m.div(dzA, dt, g.rdt()) - d2[L] + zero, zero, qo[L] - zero);
       }
-      if (zero_pivot) { errval = (float)zero_pivot; return 2; }      // :818-825
+      if (zero_pivot) { errval = (float)zero_pivot; STOP_RET(2); }   // :818-825
     }
     tri_ok = true;
   }
@@ -1903,7 +1979,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
     float qout, dqodw1, dqodw2;
     flux3(hk[1], num, dsmpdw[1], dsmpdw[2], dhkdw[1], den, rden, qout, dqodw1, dqodw2);
     const float bm1 = m.div(g.dz(1), dt, g.rdt()) + dqodw1;
-    if (bm1 == 0.0f) { errval = bm1; return 1; }                    // :806-812
+    if (bm1 == 0.0f) { errval = bm1; STOP_RET(1); }                 // :806-812
     row(1, zero, bm1, dqodw2, qflx_infl - qout - tran * ROOT(1));
     q_prev = qout; dq0_prev = dqodw1; dq1_prev = dqodw2;
   }
@@ -1939,15 +2015,41 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
       row(i + 1, -dqodw1, m.div(dzA, dt, g.rdt()) - dqodw2 + dqodw1b, zero, qout - qout1);
     }
   }
-  if (zero_pivot) { errval = (float)zero_pivot; return 2; }          // :818-825
+  if (zero_pivot) { errval = (float)zero_pivot; STOP_RET(2); }       // :818-825
   }  // !tri_ok
+  if constexpr (!kChain) {
 #pragma unroll
   for (int i = L; i >= 1; i--) dwat2[i] = dwat2[i] - GAM[i + 1] * dwat2[i + 1];
   // :845-850
 #pragma unroll
   for (int i = 1; i <= L; i++) h2o[i] = h2o[i] + dwat2[i] * g.dz(i);
+  }
   cs.launder();
   pr.mark(4);
+  // The water-table chain, :856-1123: from here to pr.mark(6).  Its results
+  // besides the state: rsub_top and the final jwt (read by the sections after
+  // it) and additions to h2osoi_liq of up to two layers (add_h2o).  The main
+  // wave of a column whose second wave takes the chain (ROLE_MAINS) runs it
+  // only for a substep that starts below the column, whose recharge is the
+  // sweep's: the branches of a water table in the column do not exist there
+  // (kOwn; no block around the text: a scope of its own moved the 22-column
+  // kernel's code), and in a substep that is the second wave's it passes over
+  // the powers of the baseflow section and takes everything from the
+  // hand-over rows below.  The second wave (kChain) posts the additions
+  // instead of adding.
+  constexpr bool kOwn = ROLE != ROLE_MAINS;
+  float rsub_top;
+  int jwt3;
+  // h2o(I) = h2o(I) + v, I at runtime: a select per layer (opaque, so it is
+  // not folded back into an indexed store that would demote h2o to scratch)
+  auto add_h2o = [&](int i, float v) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 1; j <= L; j++) {
+      int hit = (j == i);
+      opaque(hit);
+      h2o[j] = hit ? h2o[j] + v : h2o[j];
+    }
+  };
   // The specific yield s_y(I) = max(ts(I) (1 - (1 + zwtmm/(-psi(I)))^(-1/b(I))),
   // 0.02) (:963-965, :979-981, :1077-1080), for a layer i at runtime.
   auto s_y_base = [&](int i, float zmm) __attribute__((always_inline)) -> float {
@@ -1964,7 +2066,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // layer the water-table loops below visit, s_y(jwt+1) at this zwtmm, are
   // independent: one lane of the pair evaluates each.
   float qcharge, sy_first = zero;
-  if (jwt < L) {
+  if (kOwn && jwt < L) {
     H9G_BR(BR_JWTCOL);
     // operands of layer jwt+1 (and jwt): the parameters by runtime-indexed
     // store reads, the register arrays by selects
@@ -2021,7 +2123,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   if (jwt == L) {
     s.wa = s.wa + qcharge * dt;
     s.zwt = s.zwt - m.div(qcharge * dt, 1000.0f, r1000) / rous;
-  } else {
+  } else if (kOwn) {
     float qcharge_tot = qcharge * dt;
     if (qcharge_tot > zero) {          // rising: I = jwt+1 .. 1
       visit_layers(m, [&](int k) __attribute__((always_inline)) -> bool {
@@ -2061,12 +2163,17 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   zwtmm = 1000.0f * s.zwt;
   // rsub_top's exponential and the pair's power are independent: both
   // branch-free, one deferred check (before the pair exchange).
-  float rsub_top;
   const int jd = jwt2 < L ? jwt2 + 1 : L;
   FV<1> pR, pD;
   sp.template pick<1>(
       [&](int h) __attribute__((always_inline)) -> FV<1> {
         const int i = h ? jd : L;
+        if constexpr (!kOwn) {           // (the second wave's substep)
+          if (!aq) {
+            rsub_top = zero;
+            return FV<1>{{zero}};
+          }
+        }
         bool se = false, sq = false, sw = false;
         float ex = expf_fast(m, -fff * s.zwt, se);
         const float nb = -cs.lay(PF_PSI, i);
@@ -2085,25 +2192,35 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   rous = s_y_of(L, pR.v[0]);
   const float sy_drain = s_y_of(jd, pD.v[0]);
   // :1048-1118
-  int jwt3 = jwt2;
+  jwt3 = jwt2;
   if (jwt2 == L) {
     s.wa = s.wa - rsub_top * dt;
     s.zwt = s.zwt + m.div(rsub_top * dt, 1000.0f, r1000) / rous;
+    if constexpr (kChain) {              // (the same sum, by add_h2o on the main wave)
+      cs.set_ho(CS::HS_I0, (float)L);
+      cs.set_ho(CS::HS_R0, MAXF(0.0f, (s.wa - 5000.0f)));
+    } else {
     h2o[L] = h2o[L] + MAXF(0.0f, (s.wa - 5000.0f));
+    }
     s.wa = MINF(s.wa, 5000.0f);
-  } else {
+  } else if (kOwn) {
     float rsub_top_tot = -rsub_top * dt;
-    if (rsub_top_tot > zero) { errval = rsub_top_tot; return 3; }
+    if (rsub_top_tot > zero) { errval = rsub_top_tot; STOP_RET(3); }
     visit_layers(m, [&](int k) __attribute__((always_inline)) -> bool {   // I = jwt+1 .. L
       const int i = jwt2 + 1 + k;
       const float s_y = k == 0 ? sy_drain : s_y_at(i, zwtmm);
       float rstl = MAXF(rsub_top_tot, -(s_y * (cs.zi(i) - zwtmm)));
       rstl = MINF(rstl, zero);
+      if constexpr (kChain) {           // h2o(I) = h2o(I) + rstl, on the main wave
+        cs.set_ho(CS::HS_I0 + 2 * k, (float)i);
+        cs.set_ho(CS::HS_R0 + 2 * k, rstl);
+      } else {
 #pragma unroll
       for (int j = 1; j <= L; j++) {    // h2o(I) = h2o(I) + rstl, I at runtime: a select per
         int hit = (j == i);             // layer (opaque, so it is not folded back into an
         opaque(hit);                    // indexed store that would demote h2o to scratch)
         h2o[j] = hit ? h2o[j] + rstl : h2o[j];
+      }
       }
       rsub_top_tot = rsub_top_tot - rstl;
       if (rsub_top_tot >= zero) {
@@ -2120,6 +2237,35 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // :1122-1123
   s.zwt = MAXF(0.0f, s.zwt);
   s.zwt = MINC(80.0f, s.zwt);
+  if constexpr (kChain) {                // the second wave's call ends here (front_year_pair posts the state)
+    cs.set_ho(CS::HS_RSUB, rsub_top);
+    cs.set_ho(CS::HS_JWT, (float)jwt3);
+    pr.mark(6);
+    return 0;
+  }
+  if constexpr (ROLE == ROLE_MAINS) {
+    // barrier 3 (front_year_pair): the second wave's chain of this substep.
+    // Lanes 0 and 1 are here on every path but a STOP's, which passes the
+    // barrier where it returns (STOP_RET).  Stamps: with the chain on the
+    // second wave p5 is the wait here and p6 the taking over.
+    cs.wg_sync();
+    if (!aq) {
+      pr.mark(5);
+      s.zwt = cs.ho(CS::HS_ZWT);
+      s.wa = cs.ho(CS::HS_WAO);
+      rsub_top = cs.ho(CS::HS_RSUB);
+      jwt3 = (int)cs.ho(CS::HS_JWT);
+      const int scode = (int)cs.ho(CS::HS_CODE);
+      if (__builtin_expect(scode != 0, 0)) {   // the chain's STOP 3 (:1048), where the reference raises it
+        errval = cs.ho(CS::HS_ERRV);
+        return scode;
+      }
+      m.special |= cs.ho(CS::HS_FLAG) != zero;
+      const int i0 = (int)cs.ho(CS::HS_I0), i1 = (int)cs.ho(CS::HS_I1);
+      if (i0) add_h2o(i0, cs.ho(CS::HS_R0));
+      if (i1) add_h2o(i1, cs.ho(CS::HS_R1));
+    }
+  }
   cs.launder();
   pr.mark(6);
   // :1131-1137 saturation excess, bottom-up bucket
@@ -2201,6 +2347,7 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
 #undef ROOT
 #undef DC
 #undef OWN
+#undef STOP_RET
 }
 
 // The day snapshot (sv_* of the store): the state at the start of substep
@@ -2289,8 +2436,7 @@ H9K_HD int substep_pair(const G &g, CS cs, const SP &sp, St<L> &s, float &rnf_su
   const bool in_column = true;                // test builds: also below the column (-> H9G_ERR_NOSNAP)
 #endif
   // (the two-wave shape's main wave: without the front, which its front wave evaluates)
-  int code = hydrology_pair<L, G, MathFast, SP, CS, PR, CS::kFront ? ROLE_MAIN : ROLE_ALL>(g, cs, sp, s, rnf_sum,
-                                                                                            errval, mf, pr);
+  int code = hydrology_pair<L, G, MathFast, SP, CS, PR, main_role<CS>()>(g, cs, sp, s, rnf_sum, errval, mf, pr);
 #if defined(H9G_FORCE_RERUN)
   // test builds: also re-run every H9G_FORCE_RERUN-th substep of a day that
   // could (the exact replay from the day snapshot must reproduce the fast
@@ -2496,6 +2642,51 @@ constexpr bool kDays = std::is_same<MO, DaysEt>::value;
 //  - pair_body's early returns (slot past the list, non-land cell, stopped
 //    cell) are decided by both waves from the same global values before the
 //    first barrier 1; then neither wave reaches any.
+//
+// Round 10 (PairStore kSide, H9G_P1_SIDE): three barriers per substep, the
+// water-table chain (hydrology_pair, pr.mark(4) to pr.mark(6)) on the second
+// wave beside the main wave's tridiagonal sweep.  Both waves decide from the
+// posted zwt whose chain a substep's is: the second wave's when the substep
+// starts with the water table in the column (jwt < L), else the main wave's
+// as before (the recharge is then the sweep's dwat2(L+1)).
+//   main wave                             second wave
+//     front_post (and wa), go = 0
+//     barrier 1 ------------------------- barrier 1
+//     theta, rounds A, B, C                 go != 0: leave
+//     the two single powers, smp and        the front, FrontRes -> rows
+//       zq of layer max(jwt, 1) -> rows
+//     barrier 2 ------------------------- barrier 2
+//     FrontRes -> registers                 jwt < L: the chain from the rows
+//     the sweep, h2o += dwat2 dz              posted; zwt, wa, rsub_top, jwt,
+//     jwt = L: the chain                      flag, STOP 3 and its value, the
+//                                             h2o additions -> rows
+//     barrier 3 ------------------------- barrier 3
+//     jwt < L: the rows -> registers,       (waits at the next barrier 1)
+//       STOP 3, h2o additions in order
+//     saturation excess .. balance
+//   at every exit of the year loop: front_done, as above.
+// Each interval's words: the HS_* rows the main wave writes (wa before barrier
+// 1, the rest before barrier 2) are read by the second wave only between
+// barriers 2 and 3; those the second wave writes there are read by the main
+// wave only between barrier 3 and the next barrier 1.  The chain reads the
+// block's parameter fields and the geometry table besides, which nobody
+// writes during the year.
+// Why still no wave waits at a barrier its partner does not reach:
+//  - The main wave's sequence is (barrier 1, 2, 3) per substep, then one
+//    barrier 1 with go = 1; the second wave's is barrier 1, then (barrier 2,
+//    3, 1) for as long as go = 0.  Neither count depends on jwt: the second
+//    wave's chain call returns at once for jwt = L and it goes to barrier 3,
+//    and the main wave passes barrier 3 after its own chain.
+//  - The main wave's returns between barriers 2 and 3 are the sweep's STOPs 1
+//    and 2 (and, formally, its own chain's STOP 3, never reached with jwt = L):
+//    each passes barrier 3 on its way out (STOP_RET) and carries its code to
+//    cell_year_pair, which then passes front_done.  The second wave may have
+//    raised STOP 3 in the same substep: the main wave never reads those rows.
+//  - The second wave's STOP 3 does not end its loop: it posts the code and its
+//    value and goes to barrier 3; the main wave returns it after barrier 3.
+//  - H9G_ERR_NOSNAP_K and the exact re-run (ROLE_ALL, no barrier) stay behind
+//    hydrology_pair's return, after barrier 3.  The second wave's flag for the
+//    re-run (a third layer visit, a subnormal quotient) travels in HS_FLAG.
 template <int L, class SP, class CS>
 H9K_HD void front_post(const SP &sp, const CS &cs, const St<L> &s) {
 #pragma unroll
@@ -2503,6 +2694,7 @@ H9K_HD void front_post(const SP &sp, const CS &cs, const St<L> &s) {
   cs.set_ho(CS::HO_H2O1, s.h2o[1]);
   cs.set_ho(CS::HO_ZWT, s.zwt);
   cs.set_ho(CS::HO_GO, zero);
+  if constexpr (CS::kSide) cs.set_ho(CS::HS_WA, s.wa);
 }
 template <class CS>
 H9K_HD void front_done(const CS &cs) {
@@ -2535,6 +2727,24 @@ H9K_HD void front_year_pair(const G &g, CS cs, const SP &sp, const h9m::Tabs &T,
     cs.set_ho(CS::HO_EVG, fr.evg);
     cs.set_ho(CS::HO_INFL, fr.qflx_infl);
     cs.wg_sync();                                      // barrier 2
+    if constexpr (CS::kSide) {
+      // the water-table chain of a substep that starts with the water table in
+      // the column (the call returns at once for one that starts below it);
+      // pr: p5, p6 the chain, p7 the wait at barrier 3
+      cs.launder();
+      s.wa = cs.ho(CS::HS_WA);
+      cs.set_ho(CS::HS_I0, zero);
+      cs.set_ho(CS::HS_I1, zero);
+      MathFast mc{T, false};
+      const int code = hydrology_pair<L, G, MathFast, SP, CS, PR, ROLE_CHAIN>(g, cs, sp, s, rnf_sum, errval, mc, pr);
+      cs.set_ho(CS::HS_ZWT, s.zwt);
+      cs.set_ho(CS::HS_WAO, s.wa);
+      cs.set_ho(CS::HS_FLAG, mc.special ? one : zero);
+      cs.set_ho(CS::HS_CODE, (float)code);
+      cs.set_ho(CS::HS_ERRV, errval);
+      cs.wg_sync();                                    // barrier 3
+      pr.mark(7);
+    }
   }
 }
 

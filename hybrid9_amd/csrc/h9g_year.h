@@ -243,7 +243,7 @@ template <int L, class G, int R, int C = H9G_PCPW, bool MON = false, bool FRONT 
 __device__ __forceinline__ void pair_body(const KArgs &a, const G &g, float *mon = nullptr, float *dayr = nullptr) {
   static_assert(!(MON && ET), "the ET kernels record months themselves");
   static_assert(!DAY || ET, "the day kernels are ET kernels");
-  typedef PairStore<L, 2 * C, R, FRONT ? 1 : 0> PS;
+  typedef PairStore<L, 2 * C, R, FRONT ? (H9G_P1_SIDE ? 2 : 1) : 0> PS;   // (2: the water-table chain on the second wave too)
   static_assert(!FRONT || C == 1, "the front wave serves a one-column wave");
   constexpr int NW = FRONT ? 1 : H9G_PWAVES;               // column blocks per workgroup
   __shared__ uint64_t s_e2[32];
