@@ -31,8 +31,9 @@
 // other geometry-templated kernels are h9g_cols.hip.  This file is the host
 // runtime's core (h9g_ctx.h): the context's lifetime and configuration,
 // parameters, state, forcing and prefetch, the year launch with its
-// permutation and diagnostics kernels, h9g_run_year, the daily and monthly
-// recording, statistics and errors.  The ordered mode is h9g_ord.hip, spin-up
+// permutation and diagnostics kernels, h9g_run_year, the daily diagnostics,
+// the recorded outputs (RecStream: months and day records, one code path:
+// rec_begin, rec_get), statistics and errors.  The ordered mode is h9g_ord.hip, spin-up
 // h9g_spin.hip; the soil build, synthetic inputs and self-tests are
 // h9g_aux.hip.
 #include <hip/hip_runtime.h>
@@ -167,7 +168,7 @@ static std::string year_kernel_name(const h9g_ctx *ctx, int kind, size_t cells) 
   const std::string targs = "<" + L + "," + (gk == GEO_R ? "GeoR" : "GeoC<" + L + "," + std::to_string((int)gk) + ">") + ">";
   auto name = [&](int k) {
     const ShapeInfo si = shape_info(year_shape(k, cells));
-    return (ctx->days ? si.day_name : ctx->evap ? si.et_name : si.name) + targs;
+    return (ctx->rec[REC_DAY].on ? si.day_name : ctx->evap ? si.et_name : si.name) + targs;
   };
   return kind == K_MIXED ? name(K_SOLO) + "+" + name(K_PAIR) : name(kind);
 }
@@ -207,12 +208,8 @@ void h9g_destroy(h9g_ctx *ctx) {
   (void)hipFree(ctx->d_perm2);
   (void)hipFree(ctx->d_forc_s);
   (void)hipFree(ctx->d_ann_s);
-  (void)hipFree(ctx->d_mon);
-  (void)hipFree(ctx->d_mon_s);
-  (void)hipFree(ctx->d_mon_ret);
-  (void)hipFree(ctx->d_day);
-  (void)hipFree(ctx->d_day_s);
-  (void)hipFree(ctx->d_day_ret);
+  for (RecStream &s : ctx->rec)
+    for (float *p : {s.d_year, s.d_year_s, s.d_ret}) (void)hipFree(p);
   (void)hipFree(ctx->d_hist);
   (void)hipFree(ctx->d_aqbits);
   (void)hipFree(ctx->d_pace);
@@ -358,6 +355,9 @@ h9g_ctx *h9g_create(const h9g_config *cfg, int device) {
   const size_t n = ctx->n;
   const int L = ctx->L;
   ctx->ios = 2 * round_up(n, H9G_PCPW) + 64;
+  ctx->rec[REC_MON].year_rows = (size_t)H9G_NMONTHS * annual_rows(L);
+  ctx->rec[REC_DAY].year_rows = (size_t)cfg->max_days * H9G_NDAYREC;
+  ctx->rec[REC_DAY].day_rows = H9G_NDAYREC;
   bool ok = hipStreamCreateWithFlags(&ctx->sc, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&ctx->sx, hipStreamNonBlocking) == hipSuccess &&
             hipMalloc(&ctx->d_par, sizeof(float) * par_rows(L) * n) == hipSuccess &&
@@ -714,10 +714,11 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
               !g2_fits(ctx, d_list ? (size_t)m : ctx->n, (size_t)ys.k2)))
     return H9G_EINVAL;
   if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
-  const bool mon = ctx->monthly && !ys.probe;   // (a probe never records months)
-  if (mon && ((d_list && !ys.mon_dst) || (two && !ys.mon2))) return H9G_EINVAL;
-  const bool day = ctx->days && !ys.probe;      // (nor days: a probe runs on the ET kernels)
-  if (day && ((d_list && !ys.day_dst) || (two && !ys.day2))) return H9G_EINVAL;
+  bool rec[REC_N];   // what the launch records (a probe nothing: with days on it runs on the ET kernels)
+  for (int w = 0; w < REC_N; w++) {
+    rec[w] = ctx->rec[w].on && !ys.probe;
+    if (rec[w] && ((d_list && !ys.rec_dst[w]) || (two && !ys.rec2[w]))) return H9G_EINVAL;
+  }
 #if defined(H9G_DUMP_AQ)
   if (d_list || ys.st) return H9G_EINVAL;   // (the record is indexed by the annual array's cell)
 #endif
@@ -732,21 +733,11 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (two) HIPCHK(hipStreamWaitEvent(ctx->sc, ctx->ev_copied[ys.slot2], 0));
   const int n = (int)ctx->n;
   const size_t ios = ctx->ios;
-  const size_t mrows = (size_t)H9G_NMONTHS * annual_rows(ctx->L);
-  if (mon && !ctx->d_mon) {                 // NaN until a year writes it, as d_ann
-    HIPCHK(hipMalloc(&ctx->d_mon, sizeof(float) * mrows * ctx->n));
-    HIPCHK(hipMemsetAsync(ctx->d_mon, 0xff, sizeof(float) * mrows * ctx->n, ctx->sc));
-  }
-  // the day rows: every day of the longest year, so that a year's rows lie
-  // at the same place whatever its length
-  const size_t drows = (size_t)ctx->cfg.max_days * H9G_NDAYREC;
-  if (day && !ctx->d_day) {                 // NaN until a year writes it, as d_mon
-    if (hipMalloc(&ctx->d_day, sizeof(float) * drows * ctx->n) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->d_day = nullptr;
-      return H9G_ENOMEM;
-    }
-    HIPCHK(hipMemsetAsync(ctx->d_day, 0xff, sizeof(float) * drows * ctx->n, ctx->sc));
+  for (int w = 0; w < REC_N; w++) {
+    RecStream &s = ctx->rec[w];
+    if (!rec[w] || s.d_year) continue;      // NaN until a year writes it, as d_ann
+    if (int r = rec_malloc(&s.d_year, s.year_floats(ctx->n))) return r;
+    HIPCHK(hipMemsetAsync(s.d_year, 0xff, sizeof(float) * s.year_floats(ctx->n), ctx->sc));
   }
   KArgs a;
   a.ncell = n;
@@ -784,12 +775,9 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (d_list || ctx->sort) {
     if (!ctx->d_forc_s) HIPCHK(hipMalloc(&ctx->d_forc_s, sizeof(float) * 7 * (size_t)ctx->cfg.max_days * ios));
     if (!ctx->d_ann_s) HIPCHK(hipMalloc(&ctx->d_ann_s, sizeof(float) * annual_rows(ctx->L) * ios));
-    if (mon && !ctx->d_mon_s) HIPCHK(hipMalloc(&ctx->d_mon_s, sizeof(float) * mrows * ios));
-    if (day && !ctx->d_day_s && hipMalloc(&ctx->d_day_s, sizeof(float) * drows * ios) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->d_day_s = nullptr;
-      return H9G_ENOMEM;
-    }
+    for (int w = 0; w < REC_N; w++)
+      if (rec[w] && !ctx->rec[w].d_year_s)
+        if (int r = rec_malloc(&ctx->rec[w].d_year_s, ctx->rec[w].year_rows * ios)) return r;
   }
   const size_t dvar = (size_t)ctx->cfg.max_days * ios;
   // the second group from the first whole wave after the first group's
@@ -849,10 +837,10 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
 #endif
   }
   if (a.sorted_io) a.fvar = dvar;
-  // the monthly rows, addressed as a.annual
-  float *const mon_a = !mon ? nullptr : a.sorted_io ? ctx->d_mon_s : ctx->d_mon;
-  // ... and the day rows
-  float *const day_a = !day ? nullptr : a.sorted_io ? ctx->d_day_s : ctx->d_day;
+  // the recorded rows, addressed as a.annual
+  float *rec_a[REC_N];
+  for (int w = 0; w < REC_N; w++)
+    rec_a[w] = !rec[w] ? nullptr : a.sorted_io ? ctx->rec[w].d_year_s : ctx->rec[w].d_year;
   // workgroups of the launch (the pair part's, for the mixed kind)
   const size_t blocks = shape_blocks(shape, kind == K_MIXED ? ctx->n - ctx->n_solo : (size_t)a.cend);
   if (si.pair) {
@@ -913,7 +901,7 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   ctx->ev_kind[e] = ys.probe ? K_PROBE : kind;
   ctx->ev_cells[e] = (int64_t)ncells + (two ? ys.k2 : 0);
   HIPCHK(hipEventRecord(ctx->ev0[e], ctx->sc));
-  if (int r = launch_year(ctx, shape, kind == K_MIXED, a, mon_a, day_a)) return r;
+  if (int r = launch_year(ctx, shape, kind == K_MIXED, a, rec_a[REC_MON], rec_a[REC_DAY])) return r;
   // a one-column context's name is the kernel its last year ran on (the
   // launch record of the shape; until a year runs, h9g_create's)
   if (kind == K_PAIR1 && ctx->kind == K_PAIR1) ctx->kname = year_kernel_name(ctx, kind, ncells);
@@ -922,24 +910,19 @@ int run_year_impl(h9g_ctx *ctx, const YearSpec &ys) {
   if (two) HIPCHK(hipEventRecord(ctx->ev_consumed[ys.slot2], ctx->sc));
   if (a.sorted_io) {
     const unsigned rows = (unsigned)annual_rows(ctx->L);
-    h9g_unperm_annual_kernel<<<dim3((unsigned)((ncells + 255) / 256), rows), 256, 0, ctx->sc>>>(
-        (int)ncells, n, (int)rows, 0, ios, a.perm, ctx->d_ann_s, d_list ? ys.ann_dst : ctx->d_ann);
-    if (two)
-      h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
-          ys.k2, n, (int)rows, a.split, ios, a.perm, ctx->d_ann_s, ys.ann2);
-    if (mon) {
-      h9g_unperm_annual_kernel<<<dim3((unsigned)((ncells + 255) / 256), rows), 256, 0, ctx->sc>>>(
-          (int)ncells, n, (int)mrows, 0, ios, a.perm, ctx->d_mon_s, d_list ? ys.mon_dst : ctx->d_mon);
-      if (two)
-        h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
-            ys.k2, n, (int)mrows, a.split, ios, a.perm, ctx->d_mon_s, ys.mon2);
-    }
-    if (day) {                          // each group the days of its own year
-      h9g_unperm_annual_kernel<<<dim3((unsigned)((ncells + 255) / 256), rows), 256, 0, ctx->sc>>>(
-          (int)ncells, n, nt * H9G_NDAYREC, 0, ios, a.perm, ctx->d_day_s, d_list ? ys.day_dst : ctx->d_day);
-      if (two)
-        h9g_unperm_annual_kernel<<<dim3((unsigned)((ys.k2 + 255) / 256), rows), 256, 0, ctx->sc>>>(
-            ys.k2, n, nt2 * H9G_NDAYREC, a.split, ios, a.perm, ctx->d_day_s, ys.day2);
+    // nrows rows of the launch's first group, or of its second (the k2 slots from a.split), back to cell order
+    auto unperm = [&](bool second, size_t nrows, const float *src, float *dst) {
+      const size_t cells = second ? (size_t)ys.k2 : ncells;
+      h9g_unperm_annual_kernel<<<dim3((unsigned)((cells + 255) / 256), rows), 256, 0, ctx->sc>>>(
+          (int)cells, n, (int)nrows, second ? a.split : 0, ios, a.perm, src, dst);
+    };
+    unperm(false, rows, ctx->d_ann_s, d_list ? ys.ann_dst : ctx->d_ann);
+    if (two) unperm(true, rows, ctx->d_ann_s, ys.ann2);
+    for (int w = 0; w < REC_N; w++) {     // each group the rows of its own year
+      const RecStream &s = ctx->rec[w];
+      if (!rec[w]) continue;
+      unperm(false, s.rows_written(nt), s.d_year_s, d_list ? ys.rec_dst[w] : s.d_year);
+      if (two) unperm(true, s.rows_written(nt2), s.d_year_s, ys.rec2[w]);
     }
     HIPCHK(hipGetLastError());
   }
@@ -1094,17 +1077,15 @@ int h9g_run_year(h9g_ctx *ctx, int slot, int jyear) {
   YearSpec ys;
   ys.slot = slot;
   ys.jyear = jyear;
-  if (ctx) ctx->mon_years = 0;
-  if (ctx) ctx->day_nt.clear();
+  if (ctx)
+    for (RecStream &s : ctx->rec) s.nt.clear();
   const int r = run_year_impl(ctx, ys);
-  if (r == 0 && ctx->monthly) {
-    ctx->mon_years = 1;
-    ctx->mon_in_ret = false;
-  }
-  if (r == 0 && ctx->days) {
-    ctx->day_nt.assign(1, days_in_year(jyear));
-    ctx->day_in_ret = false;
-  }
+  if (r == 0)
+    for (RecStream &s : ctx->rec)
+      if (s.on) {
+        s.nt.assign(1, days_in_year(jyear));
+        s.in_ret = false;
+      }
   return r;
 }
 
@@ -1115,8 +1096,8 @@ int h9g_set_monthly(h9g_ctx *ctx, int on) {
 #endif
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
-  ctx->monthly = on ? 1 : 0;
-  ctx->mon_years = 0;
+  ctx->rec[REC_MON].on = on ? 1 : 0;
+  ctx->rec[REC_MON].nt.clear();
   return 0;
 }
 
@@ -1129,7 +1110,7 @@ int h9g_set_evap(h9g_ctx *ctx, int on) {
 #if defined(H9G_STAMPS)
   if (on) return H9G_EINVAL;   // (as h9g_set_monthly)
 #endif
-  if (!on && ctx->days) return H9G_ESTATE;   // day recording rides on the ET sum (h9g_set_days)
+  if (!on && ctx->rec[REC_DAY].on) return H9G_ESTATE;  // day recording rides on the ET sum (h9g_set_days)
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   if (ctx->evap != (on ? 1 : 0)) {
@@ -1142,17 +1123,20 @@ int h9g_set_evap(h9g_ctx *ctx, int on) {
   return 0;
 }
 
-int h9g_get_monthly(h9g_ctx *ctx, int k, float *out) {
+// Year k of what the last call recorded of stream `which`: the rows that year wrote.
+static int rec_get(h9g_ctx *ctx, int which, int k, float *out) {
   if (!ctx || !out) return H9G_EINVAL;
-  if (ctx->mon_years < 1) return H9G_ESTATE;
-  if (k < 0 || k >= ctx->mon_years) return H9G_EINVAL;
+  const RecStream &s = ctx->rec[which];
+  if (s.nt.empty()) return H9G_ESTATE;
+  if (k < 0 || (size_t)k >= s.nt.size()) return H9G_EINVAL;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
-  const size_t year = (size_t)H9G_NMONTHS * annual_rows(ctx->L) * ctx->n;
-  HIPCHK(hipMemcpy(out, ctx->mon_in_ret ? ctx->d_mon_ret + (size_t)k * year : ctx->d_mon, sizeof(float) * year,
-                   hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, s.in_ret ? s.ret_year(ctx->n, k) : s.d_year,
+                   sizeof(float) * s.rows_written(s.nt[(size_t)k]) * ctx->n, hipMemcpyDeviceToHost));
   return 0;
 }
+
+int h9g_get_monthly(h9g_ctx *ctx, int k, float *out) { return rec_get(ctx, REC_MON, k, out); }
 
 // Day records (include/h9g.h): needs ET recording on.  The context's name
 // follows (h9g_kernel_name: the day kernels').
@@ -1164,61 +1148,33 @@ int h9g_set_days(h9g_ctx *ctx, int on) {
   if (on && !ctx->evap) return H9G_ESTATE;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
-  if (ctx->days != (on ? 1 : 0)) {
-    ctx->days = on ? 1 : 0;
+  RecStream &s = ctx->rec[REC_DAY];
+  if (s.on != (on ? 1 : 0)) {
+    s.on = on ? 1 : 0;
     const std::string from = on ? "_et_kernel" : "_day_kernel", to = on ? "_day_kernel" : "_et_kernel";
     for (size_t p = 0; (p = ctx->kname.find(from, p)) != std::string::npos; p += to.size())
       ctx->kname.replace(p, from.size(), to);
   }
-  ctx->day_nt.clear();
+  s.nt.clear();
   return 0;
 }
 
-int h9g_get_days(h9g_ctx *ctx, int k, float *out) {
-  if (!ctx || !out) return H9G_EINVAL;
-  if (ctx->day_nt.empty()) return H9G_ESTATE;
-  if (k < 0 || (size_t)k >= ctx->day_nt.size()) return H9G_EINVAL;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->sc));
-  const size_t year = (size_t)ctx->cfg.max_days * H9G_NDAYREC * ctx->n;
-  HIPCHK(hipMemcpy(out, ctx->day_in_ret ? ctx->d_day_ret + (size_t)k * year : ctx->d_day,
-                   sizeof(float) * (size_t)ctx->day_nt[(size_t)k] * H9G_NDAYREC * ctx->n, hipMemcpyDeviceToHost));
-  return 0;
-}
+int h9g_get_days(h9g_ctx *ctx, int k, float *out) { return rec_get(ctx, REC_DAY, k, out); }
 
-// Room for the day records of an ordered call's `nyears` years; none recorded yet.
-int day_begin(h9g_ctx *ctx, int nyears) {
-  ctx->day_nt.clear();
-  ctx->day_base = 0;
-  if (ctx->day_ret_cap >= (size_t)nyears) return 0;
-  HIPCHK(hipStreamSynchronize(ctx->sc));
-  (void)hipFree(ctx->d_day_ret);
-  ctx->d_day_ret = nullptr;
-  ctx->day_ret_cap = 0;
-  if (hipMalloc(&ctx->d_day_ret, sizeof(float) * (size_t)nyears * ctx->cfg.max_days * H9G_NDAYREC * ctx->n) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return H9G_ENOMEM;
+// An ordered call of `nyears` years begins: room for them in the retained
+// buffer of every recording that is on; none recorded yet.
+int rec_begin(h9g_ctx *ctx, int nyears) {
+  for (RecStream &s : ctx->rec) {
+    if (!s.on) continue;
+    s.nt.clear();
+    s.base = 0;
+    if (s.ret_cap >= (size_t)nyears) continue;
+    HIPCHK(hipStreamSynchronize(ctx->sc));
+    (void)hipFree(s.d_ret);
+    s.ret_cap = 0;
+    if (int r = rec_malloc(&s.d_ret, (size_t)nyears * s.year_floats(ctx->n))) return r;
+    s.ret_cap = (size_t)nyears;
   }
-  ctx->day_ret_cap = (size_t)nyears;
-  return 0;
-}
-
-// Room for the snapshots of an ordered call's `nyears` years; none recorded yet.
-int mon_begin(h9g_ctx *ctx, int nyears) {
-  ctx->mon_years = 0;
-  ctx->mon_base = 0;
-  if (ctx->mon_ret_cap >= (size_t)nyears) return 0;
-  HIPCHK(hipStreamSynchronize(ctx->sc));
-  (void)hipFree(ctx->d_mon_ret);
-  ctx->d_mon_ret = nullptr;
-  ctx->mon_ret_cap = 0;
-  if (hipMalloc(&ctx->d_mon_ret, sizeof(float) * (size_t)nyears * H9G_NMONTHS * annual_rows(ctx->L) * ctx->n) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return H9G_ENOMEM;
-  }
-  ctx->mon_ret_cap = (size_t)nyears;
   return 0;
 }
 

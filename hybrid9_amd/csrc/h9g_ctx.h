@@ -1,5 +1,6 @@
 // h9g_ctx.h -- what the host runtime's units share (not ABI): the context,
-// the year launch's description and the few functions that cross units.
+// the description of a recorded output (RecStream) and of a year launch
+// (YearSpec), and the few functions that cross units.
 // Included by h9g.hip (context, forcing, the year launch, recording),
 // h9g_ord.hip (the ordered mode), h9g_spin.hip (spin-up) and h9g_aux.hip (soil
 // build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
@@ -25,6 +26,39 @@ static inline int days_in_year(int y) {   // INIT.f90:844-859
 }
 
 static inline unsigned nblocks(size_t n) { return (unsigned)((n + H9G_BLOCK - 1) / H9G_BLOCK); }
+
+// One recorded per-cell output beside the annual means: a year kernel writes
+// it as rows of n addressed as the annual rows are (d_ann / d_ann_s), every
+// year launch passes its destinations beside the annual ones (YearSpec), and
+// the ordered mode keeps it per decade beside the annual means (OrdDec::rec)
+// and per call in a retained buffer.  Two streams: a year's month-end
+// snapshots, 12 x annual rows; and its day records, H9G_NDAYREC rows a day at
+// max_days a year, so that a year's rows lie at the same place whatever its
+// length.  The streams differ in those two row counts (h9g_create) and in
+// nothing else.
+enum { REC_MON, REC_DAY, REC_N };
+struct RecStream {
+  int on = 0;                     // recording on
+  size_t year_rows = 0;           // rows of n a year occupies
+  int day_rows = 0;               // rows each day of a year writes; 0: every year writes all year_rows
+  float *d_year = nullptr;        // a year's rows (as d_ann; NaN until a year writes them)
+  float *d_year_s = nullptr;      // ... in slot order (as d_ann_s)
+  float *d_ret = nullptr;         // an ordered call's years, (years, year_rows, n)
+  size_t ret_cap = 0;             // years allocated there
+  int base = 0;                   // first year of the running ordered call there
+  std::vector<int> nt;            // days of each year recorded by the last call (empty: none)
+  bool in_ret = false;            // ... in d_ret (an ordered call) or d_year (h9g_run_year)
+  size_t year_floats(size_t n) const { return year_rows * n; }
+  size_t rows_written(int days) const { return day_rows ? (size_t)days * day_rows : year_rows; }
+  float *ret_year(size_t n, int k) const { return d_ret + (size_t)k * year_floats(n); }
+};
+// Every buffer of a recording: H9G_ENOMEM where it does not fit (include/h9g.h).
+static inline int rec_malloc(float **p, size_t floats) {
+  if (hipMalloc(p, sizeof(float) * floats) == hipSuccess) return 0;
+  (void)hipGetLastError();
+  *p = nullptr;
+  return H9G_ENOMEM;
+}
 
 struct h9g_ctx {
   h9g_config cfg;
@@ -102,28 +136,14 @@ struct h9g_ctx {
   size_t fyrs_cap = 0;
   std::vector<FocusYear> h_fyrs;
   std::vector<int> daily_nt;      // days of each year recorded by the last call
-  // monthly output (h9g_set_monthly / h9g_get_monthly; the monthly kernels)
-  int monthly = 0;                // recording on
-  float *d_mon = nullptr;         // a year's month-end snapshots, 12 x annual rows of n (as d_ann)
-  float *d_mon_s = nullptr;       // ... in slot order (as d_ann_s)
-  float *d_mon_ret = nullptr;     // an ordered call's years, (years, 12, annual rows, n)
-  size_t mon_ret_cap = 0;         // years allocated there
-  int mon_base = 0;               // first year of the running ordered call there
-  int mon_years = 0;              // years recorded by the last call (0: none)
-  bool mon_in_ret = false;        // ... in d_mon_ret (an ordered call) or d_mon (h9g_run_year)
+  // the recorded per-cell outputs (RecStream): months (h9g_set_monthly /
+  // h9g_get_monthly; the monthly kernels) and day records (h9g_set_days /
+  // h9g_get_days; the day kernels; on only with evap on)
+  RecStream rec[REC_N];
+  bool recording() const { return rec[REC_MON].on || rec[REC_DAY].on; }
   // evapotranspiration output (h9g_set_evap; the ET kernels): row evap of the
   // annual and monthly rows is the year's evaporation sum.  No buffer of its own.
   int evap = 0;
-  // day records (h9g_set_days / h9g_get_days; the day kernels): a year's
-  // H9G_NDAYREC values per cell and day
-  int days = 0;                   // recording on (then evap is on)
-  float *d_day = nullptr;         // a year's records, max_days x 7 rows of n (as d_ann)
-  float *d_day_s = nullptr;       // ... in slot order (as d_ann_s)
-  float *d_day_ret = nullptr;     // an ordered call's years, (years, max_days, 7, n)
-  size_t day_ret_cap = 0;         // years allocated there
-  int day_base = 0;               // first year of the running ordered call there
-  std::vector<int> day_nt;        // days of each year recorded by the last call (empty: none)
-  bool day_in_ret = false;        // ... in d_day_ret (an ordered call) or d_day (h9g_run_year)
   struct SpinBufs *spin = nullptr;   // h9g_spinup's buffers (h9g_spin.hip); null until its first call
 };
 
@@ -133,8 +153,7 @@ struct YearSpec {
   const int *d_list = nullptr;   // null: every cell, in h9g_sort_kernel's order; else the m cells d_list[0..m)
   int m = 0;
   float *ann_dst = nullptr;      // list launches: their annual means into these rows (stride n, cell order)
-  float *mon_dst = nullptr;      // ... and, with monthly recording on, their month-end snapshots into these
-  float *day_dst = nullptr;      // ... and, with day recording on, their day records into these (max_days x 7 rows)
+  float *rec_dst[REC_N] = {};    // ... and the rows of every recording that is on into these
   float *st = nullptr;           // the cells' state and STOP rows (null: the context's own)
   int *err = nullptr;
   bool bulk = false;             // a list launch that is a year of the context's cells (h9g_run_ordered's
@@ -142,12 +161,11 @@ struct YearSpec {
                                  // context's kernel, sort history and diagnostics, as an every-cell launch
   // launches of a pair kernel (g2_fits): a second group of the k2 cells
   // h2[0..k2) (host) at year jyear2 from slot2, with state st2/err2, annual
-  // means into ann2 (h9g_run_ordered: a decade's re-runs riding in the next
-  // decade's years)
+  // means into ann2 and the rows of every recording that is on into rec2
+  // (h9g_run_ordered: a decade's re-runs riding in the next decade's years)
   const int *h2 = nullptr;
   int k2 = 0, slot2 = 0, jyear2 = 0;
-  float *st2 = nullptr, *ann2 = nullptr, *mon2 = nullptr;   // (mon2: with monthly recording on)
-  float *day2 = nullptr;                                    // (with day recording on)
+  float *st2 = nullptr, *ann2 = nullptr, *rec2[REC_N] = {};
   int *err2 = nullptr;
   // list launches: only the year's first `ndays` days (0: all), the annual
   // rows as undivided running sums (the cell order's day-1 probe)
@@ -166,8 +184,7 @@ H9G_LOCAL int join_prefetch(h9g_ctx *ctx, int slot);
 H9G_LOCAL int daily_begin(h9g_ctx *ctx, int jyear0, int nyears);
 H9G_LOCAL int daily_launch(h9g_ctx *ctx, const float *st, const float *guess, const int *err, const int32_t *slots,
                            int jyear0, int ny);
-H9G_LOCAL int mon_begin(h9g_ctx *ctx, int nyears);
-H9G_LOCAL int day_begin(h9g_ctx *ctx, int nyears);
+H9G_LOCAL int rec_begin(h9g_ctx *ctx, int nyears);
 H9G_LOCAL int diag_launch(h9g_ctx *ctx);
 // h9g_ord.hip
 H9G_LOCAL void ord_free(h9g_ctx *ctx);

@@ -5,7 +5,8 @@
 #include "h9g_year.h"
 
 // The cell order: the cells that start a decade stopped (err0) run none
-// of its years; all their monthly rows of the decade (`rows` of n) are NaN.
+// of its years; all their recorded rows of the decade (`rows` of n: months
+// or day records, h9g_nan_stopped_rows) are NaN.
 __global__ void __launch_bounds__(256) h9g_stopped_mon_kernel(int n, int rows, const int *__restrict__ err0,
                                                               float *__restrict__ mon) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -13,8 +14,8 @@ __global__ void __launch_bounds__(256) h9g_stopped_mon_kernel(int n, int rows, c
   for (int r = 0; r < rows; r++) mon[(size_t)r * n + c] = __builtin_nanf("");
 }
 
-int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream) {
-  h9g_stopped_mon_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(n, rows, err0, mon);
+int h9g_nan_stopped_rows(int n, int rows, const int *err0, float *dst, hipStream_t stream) {
+  h9g_stopped_mon_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(n, rows, err0, dst);
   return 0;
 }
 

@@ -1,8 +1,9 @@
 // h9g_ord.hip -- the ordered mode: the reference's own cell order
 // (h9g_run_ordered, h9g_run_decade_ordered, h9g_set_chains and their
 // statistics) with its small kernels, on top of the year launch of h9g.hip
-// (run_year_impl, h9g_ctx.h).  Host code and seconds to compile: no year
-// kernel is instantiated here.
+// (run_year_impl, h9g_ctx.h).  Every recording that is on (RecStream) rides
+// beside the annual means: OrdDec::rec, ord_rec.  Host code and seconds to
+// compile: no year kernel is instantiated here.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
@@ -205,10 +206,8 @@ extern "C" {
 struct OrdDec {
   int y0 = 0, ny = 0, k0 = 0;            // first year, years, index of its first year in the call
   float *st0 = nullptr, *guess = nullptr, *ann = nullptr, *ck = nullptr;
-  float *mon = nullptr;                  // monthly recording: the snapshots beside ann, (years, 12, annual rows, n)
-  int mon_cap = 0;                       // years allocated there
-  float *day = nullptr;                  // day recording: the day records beside ann, (years, max_days, 7, n)
-  int day_cap = 0;                       // years allocated there
+  float *rec[REC_N] = {};                // the recordings beside ann, each (years, its rows of a year, n); null
+  int rec_cap = 0;                       // until its stream is on in a call (ord_rec_alloc); years of each
   int *err0 = nullptr, *eck = nullptr, *dirty = nullptr;
   int *d_chain = nullptr, *d_pred = nullptr, *d_first = nullptr, *d_list = nullptr, *d_flag = nullptr;
   std::vector<int> chain, list, flag;
@@ -233,7 +232,8 @@ void ord_free(h9g_ctx *ctx) {
   OrdBufs *o = ctx->ord;
   if (!o) return;
   for (OrdDec &D : o->d) {
-    for (float *p : {D.st0, D.guess, D.ann, D.ck, D.mon, D.day}) (void)hipFree(p);
+    for (float *p : {D.st0, D.guess, D.ann, D.ck}) (void)hipFree(p);
+    for (float *p : D.rec) (void)hipFree(p);
     for (int *p : {D.err0, D.eck, D.dirty, D.d_chain, D.d_pred, D.d_first, D.d_list, D.d_flag}) (void)hipFree(p);
   }
   (void)hipFree(o->st2);
@@ -292,42 +292,27 @@ static float *ord_ck(const h9g_ctx *ctx, const OrdDec &D, int y) {
 }
 static int *ord_eck(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.eck + (size_t)y * STOP_ROWS * ctx->n; }
 static float *ord_ann(const h9g_ctx *ctx, const OrdDec &D, int y) { return D.ann + (size_t)y * annual_rows(ctx->L) * ctx->n; }
-// The monthly rows of a decade's year: they live beside its annual rows, and
-// every launch that writes the one writes the other (null with recording off).
-static float *ord_mon(const h9g_ctx *ctx, const OrdDec &D, int y) {
-  return ctx->monthly ? D.mon + (size_t)y * H9G_NMONTHS * annual_rows(ctx->L) * ctx->n : nullptr;
+// The rows of recording `which` (RecStream) of a decade's year: they live
+// beside its annual rows, and every launch that writes the one writes the
+// other (null with that recording off).
+static float *ord_rec(const h9g_ctx *ctx, const OrdDec &D, int which, int y) {
+  const RecStream &s = ctx->rec[which];
+  return s.on ? D.rec[which] + (size_t)y * s.year_floats(ctx->n) : nullptr;
 }
-static int ord_mon_alloc(h9g_ctx *ctx, int ny) {
+// Room for ny years of every recording that is on, in both decades' buffers.
+// A decade's buffers all hold rec_cap years: to grow, all of them go.
+static int ord_rec_alloc(h9g_ctx *ctx, int ny) {
   for (OrdDec &D : ctx->ord->d) {
-    if (D.mon && D.mon_cap >= ny) continue;
-    (void)hipFree(D.mon);
-    D.mon = nullptr;
-    D.mon_cap = 0;
-    if (hipMalloc(&D.mon, sizeof(float) * (size_t)ny * H9G_NMONTHS * annual_rows(ctx->L) * ctx->n) != hipSuccess) {
-      (void)hipGetLastError();
-      return H9G_ENOMEM;
+    if (D.rec_cap < ny) {
+      for (float *&p : D.rec) {
+        (void)hipFree(p);
+        p = nullptr;
+      }
+      D.rec_cap = ny;
     }
-    D.mon_cap = ny;
-  }
-  return 0;
-}
-
-// The day rows of a decade's year (h9g_set_days), likewise.
-static size_t ord_day_year(const h9g_ctx *ctx) { return (size_t)ctx->cfg.max_days * H9G_NDAYREC * ctx->n; }
-static float *ord_day(const h9g_ctx *ctx, const OrdDec &D, int y) {
-  return ctx->days ? D.day + (size_t)y * ord_day_year(ctx) : nullptr;
-}
-static int ord_day_alloc(h9g_ctx *ctx, int ny) {
-  for (OrdDec &D : ctx->ord->d) {
-    if (D.day && D.day_cap >= ny) continue;
-    (void)hipFree(D.day);
-    D.day = nullptr;
-    D.day_cap = 0;
-    if (hipMalloc(&D.day, sizeof(float) * (size_t)ny * ord_day_year(ctx)) != hipSuccess) {
-      (void)hipGetLastError();
-      return H9G_ENOMEM;
-    }
-    D.day_cap = ny;
+    for (int w = 0; w < REC_N; w++)
+      if (ctx->rec[w].on && !D.rec[w])
+        if (int r = rec_malloc(&D.rec[w], (size_t)D.rec_cap * ctx->rec[w].year_floats(ctx->n))) return r;
   }
   return 0;
 }
@@ -502,8 +487,7 @@ static int ord_run_alone(h9g_ctx *ctx, OrdDec &D, const int32_t *slots, OrdStats
   ys.d_list = D.d_list;
   ys.m = (int)D.list.size();
   ys.ann_dst = ord_ann(ctx, D, D.next_y);
-  ys.mon_dst = ord_mon(ctx, D, D.next_y);
-  ys.day_dst = ord_day(ctx, D, D.next_y);
+  for (int w = 0; w < REC_N; w++) ys.rec_dst[w] = ord_rec(ctx, D, w, D.next_y);
   ys.st = ctx->ord->st2;
   ys.err = ctx->ord->err2;
   if (int r = run_year_impl(ctx, ys)) return r;
@@ -554,20 +538,19 @@ static int ord_finish(h9g_ctx *ctx, OrdDec &D, OrdDec *N, float *annual, int &st
       break;
     }
   }
-  if (ctx->monthly)       // the settled decade's months into the call's retained buffer
-    HIPCHK(hipMemcpyAsync(ctx->d_mon_ret + (size_t)(ctx->mon_base + D.k0) * H9G_NMONTHS * rows * n, D.mon,
-                          sizeof(float) * (size_t)D.ny * H9G_NMONTHS * rows * n, hipMemcpyDeviceToDevice, ctx->sc));
-  if (ctx->days)          // ... and its day records
-    HIPCHK(hipMemcpyAsync(ctx->d_day_ret + (size_t)(ctx->day_base + D.k0) * ord_day_year(ctx), D.day,
-                          sizeof(float) * (size_t)D.ny * ord_day_year(ctx), hipMemcpyDeviceToDevice, ctx->sc));
+  for (int w = 0; w < REC_N; w++)   // the settled decade's recordings into the call's retained buffers
+    if (const RecStream &s = ctx->rec[w]; s.on)
+      HIPCHK(hipMemcpyAsync(s.ret_year(n, s.base + D.k0), D.rec[w], sizeof(float) * (size_t)D.ny * s.year_floats(n),
+                            hipMemcpyDeviceToDevice, ctx->sc));
   if (N) {
     h9g_settle_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->sc>>>(
         (int)n, srows, rows, N->ny, ord_ck(ctx, D, D.ny - 1), ord_eck(ctx, D, D.ny - 1), N->st0, N->err0, N->dirty,
         ctx->d_st, ctx->d_err, ord_ck(ctx, *N, N->ny - 1), ord_eck(ctx, *N, N->ny - 1), N->ann);
-    // NaN months where it wrote NaN means: a cell that starts N stopped runs
+    // NaN recorded rows where it wrote NaN means: a cell that starts N stopped runs
     // none of N's years (N's first pass is done, and its chains leave it out)
-    if (ctx->monthly) h9g_mon_stopped((int)n, N->ny * H9G_NMONTHS * rows, N->err0, N->mon, ctx->sc);
-    if (ctx->days) h9g_mon_stopped((int)n, N->ny * ctx->cfg.max_days * H9G_NDAYREC, N->err0, N->day, ctx->sc);
+    for (int w = 0; w < REC_N; w++)
+      if (ctx->rec[w].on)
+        h9g_nan_stopped_rows((int)n, N->ny * (int)ctx->rec[w].year_rows, N->err0, N->rec[w], ctx->sc);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(ctx->sc));
@@ -613,10 +596,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->sc));
   if (int r = ord_alloc(ctx, nymax)) return r;
-  if (ctx->monthly)
-    if (int r = ord_mon_alloc(ctx, nymax)) return r;
-  if (ctx->days)
-    if (int r = ord_day_alloc(ctx, nymax)) return r;
+  if (int r = ord_rec_alloc(ctx, nymax)) return r;
   OrdBufs *o = ctx->ord;
   // land cells (HYBRID9.f90:122-123, summed in layer order as the year
   // kernels do)
@@ -685,8 +665,7 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
         ys.m = nb;
         ys.bulk = true;
         ys.ann_dst = ctx->d_ann;
-        ys.mon_dst = ctx->d_mon;
-        ys.day_dst = ctx->d_day;
+        for (int w = 0; w < REC_N; w++) ys.rec_dst[w] = ctx->rec[w].d_year;
       }
       const bool ride = P && P->phase == OrdDec::RERUN && g2_fits(ctx, (size_t)nb, P->list.size()) &&
                         !ctx->no_ride;
@@ -698,18 +677,15 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
         ys.st2 = o->st2;
         ys.err2 = o->err2;
         ys.ann2 = ord_ann(ctx, *P, P->next_y);
-        ys.mon2 = ord_mon(ctx, *P, P->next_y);
-        ys.day2 = ord_day(ctx, *P, P->next_y);
+        for (int w = 0; w < REC_N; w++) ys.rec2[w] = ord_rec(ctx, *P, w, P->next_y);
       }
       if (int r = run_year_impl(ctx, ys)) return r;
       S.ticks++;
       HIPCHK(hipMemcpyAsync(ord_ann(ctx, D, y), ctx->d_ann, sizeof(float) * rows * n, hipMemcpyDeviceToDevice, ctx->sc));
-      if (ctx->monthly)
-        HIPCHK(hipMemcpyAsync(ord_mon(ctx, D, y), ctx->d_mon, sizeof(float) * H9G_NMONTHS * rows * n,
-                              hipMemcpyDeviceToDevice, ctx->sc));
-      if (ctx->days)
-        HIPCHK(hipMemcpyAsync(ord_day(ctx, D, y), ctx->d_day, sizeof(float) * ord_day_year(ctx), hipMemcpyDeviceToDevice,
-                              ctx->sc));
+      for (int w = 0; w < REC_N; w++)
+        if (const RecStream &s = ctx->rec[w]; s.on)
+          HIPCHK(hipMemcpyAsync(ord_rec(ctx, D, w, y), s.d_year, sizeof(float) * s.year_floats(n), hipMemcpyDeviceToDevice,
+                                ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_ck(ctx, D, y), ctx->d_st, sizeof(float) * srows * n, hipMemcpyDeviceToDevice, ctx->sc));
       HIPCHK(hipMemcpyAsync(ord_eck(ctx, D, y), ctx->d_err, sizeof(int) * STOP_ROWS * n, hipMemcpyDeviceToDevice, ctx->sc));
       if (ride) {
@@ -773,14 +749,11 @@ static int run_ordered_impl(h9g_ctx *ctx, const int32_t *slots, int jyear0,
                          S.alone_cell_years, S.excluded, S.probed, S.probe_kept};
   std::copy(os, os + 9, ctx->ord_stats);
   ctx->ord_passes = S.dec_passes;
-  if (ctx->monthly) {
-    ctx->mon_years = ctx->mon_base + nyears;
-    ctx->mon_in_ret = true;
-  }
-  if (ctx->days) {
-    ctx->day_nt.resize((size_t)ctx->day_base);
-    for (int y = 0; y < nyears; y++) ctx->day_nt.push_back(days_in_year(jyear0 + y));
-    ctx->day_in_ret = true;
+  for (RecStream &s : ctx->rec) {
+    if (!s.on) continue;
+    s.nt.resize((size_t)s.base);
+    for (int y = 0; y < nyears; y++) s.nt.push_back(days_in_year(jyear0 + y));
+    s.in_ret = true;
   }
   // the first STOP of the call (h9g_last_error) or one from before it
   return h9g_sync(ctx);
@@ -806,19 +779,15 @@ int h9g_run_decade_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int n
     HIPCHK(hipSetDevice(ctx->device));
     if (int r = daily_begin(ctx, jyear0, nyears)) return r;
   }
-  if (ctx && ctx->monthly)
-    if (int r = mon_begin(ctx, nyears)) return r;
-  if (ctx && ctx->days)
-    if (int r = day_begin(ctx, nyears)) return r;
+  if (ctx)
+    if (int r = rec_begin(ctx, nyears)) return r;
   return run_ordered_impl(ctx, slots, jyear0, {{jyear0, nyears}}, annual, passes);
 }
 
 int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, float *annual, int32_t *passes) {
   if (nyears < 1 || jyear0 < 1861) return H9G_EINVAL;
-  if (ctx && ctx->monthly)
-    if (int r = mon_begin(ctx, nyears)) return r;
-  if (ctx && ctx->days)
-    if (int r = day_begin(ctx, nyears)) return r;
+  if (ctx)
+    if (int r = rec_begin(ctx, nyears)) return r;
   if (ctx && !ctx->daily_sel.empty()) {
     // with a selection the decades run one after another, each as
     // h9g_run_decade_ordered runs it (the same results bit for bit), and each
@@ -832,8 +801,7 @@ int h9g_run_ordered(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, 
     const size_t rows = annual_rows(ctx->L);
     int first = 0, k0 = 0, i = 0;
     for (const auto &d : ref_decades(jyear0, nyears)) {
-      ctx->mon_base = k0;
-      ctx->day_base = k0;
+      for (RecStream &s : ctx->rec) s.base = k0;
       const int r = run_ordered_impl(ctx, slots + k0, d.first, {d}, annual ? annual + (size_t)k0 * rows * ctx->n : nullptr,
                                      passes ? passes + i : nullptr);
       if (r < 0) return r;

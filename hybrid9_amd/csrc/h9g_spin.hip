@@ -220,7 +220,7 @@ int h9g_spinup(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, const
     for (int y = 0; y < nyears; y++)
       if (slots[y] < 0 || slots[y] >= ctx->cfg.nslots || used[(size_t)slots[y]]++) return H9G_EINVAL;
   }
-  if (!ctx->daily_sel.empty() || ctx->monthly || ctx->days) return H9G_ESTATE;   // spin-up records nothing
+  if (!ctx->daily_sel.empty() || ctx->recording()) return H9G_ESTATE;   // spin-up records nothing
   if (!ctx->params_set || !ctx->state_set) return H9G_ESTATE;
   for (int y = 0; y < nyears; y++) {
     if (const int prc = join_prefetch(ctx, slots[y])) return prc;
@@ -236,7 +236,6 @@ int h9g_spinup(h9g_ctx *ctx, const int32_t *slots, int jyear0, int nyears, const
   if (int r = spin_test(ctx, opts, 0, jyear0, stats)) return r;
   int m = (int)stats[6];     // the active cells (s->list)
   bool left = false;         // a cell has left the run: the years are list launches from here on
-  ctx->mon_years = 0;
   for (int k = 1; k <= opts->max_cycles && m > 0; k++) {
     for (int y = 0; y < nyears; y++) {
       YearSpec ys;

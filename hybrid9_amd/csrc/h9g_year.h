@@ -633,13 +633,13 @@ int launch_shape(Shape shape, const h9g_config &cfg, hipStream_t stream, const K
 // the kernel units' host side: what the host runtime (h9g_ctx.h) calls
 // ---------------------------------------------------------------------------
 // h9g_plain.hip: launch_shape<V_PLAIN>.  h9g_mon.hip: launch_shape<V_MON>, and
-// the cell order's NaN rows of the cells that start a decade stopped.
+// the cell order's NaN recorded rows of the cells that start a decade stopped.
 // h9g_et.hip: launch_shape<V_ET>.  h9g_day.hip: launch_shape<V_DAY>.
 int h9g_plain_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a);
 int h9g_mon_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
 int h9g_et_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon);
 int h9g_day_launch(Shape shape, const h9g_config *cfg, hipStream_t stream, const KArgs &a, float *mon, float *day);
-int h9g_mon_stopped(int n, int rows, const int *err0, float *mon, hipStream_t stream);
+int h9g_nan_stopped_rows(int n, int rows, const int *err0, float *dst, hipStream_t stream);
 
 // Not exported from libh9g.so.
 #define H9G_LOCAL __attribute__((visibility("hidden")))

@@ -278,7 +278,8 @@ int h9g_get_daily(h9g_ctx *ctx, int k, float *out);
  * annual means, state, STOP records and daily lines are the same bit for bit
  * either way.  The snapshots take nyears x 12 x (12+L) x ncell floats of
  * device memory per call (1.3 GB for 20 years of the 0.5 deg grid), allocated
- * by the run and released with the context (not part of h9g_config_bytes). */
+ * by the run and released with the context (not part of h9g_config_bytes);
+ * H9G_ENOMEM if it does not fit. */
 #define H9G_NMONTHS 12
 int h9g_set_monthly(h9g_ctx *ctx, int on);
 /* Snapshots of year k (0-based) of the last h9g_run_year (k = 0),

@@ -267,7 +267,68 @@ def test_cell_order_stop():
     assert np.isfinite(d[ys, :e, :, c]).all() and np.isfinite(d[:ys, :365, :, c]).all()
 
 
-# ---- 10. the Fortran host ----------------------------------------------------------
+# ---- 10. one context, several calls: the recording buffers' lifetime ---------------
+def test_recordings_across_calls_on_one_context():
+    """A context that is reused -- an ordered call with months, a longer one
+    with day records switched on beside them (the retained buffers of both
+    regrow; the day records' decade buffers come after the ordered mode's own),
+    then months off and a single year -- gives after every call the months and
+    day records a fresh context gives for the same years from the same start,
+    bit for bit, and refuses the year one past the last."""
+    meta, inp, _ = load_golden("co_c1_30yr")
+    n, L = 8, inp["params"]["theta_s"].shape[1]
+    assert inp.get("state0") is None
+    params = {k: v[:n] for k, v in inp["params"].items()}
+    d0 = np.concatenate([[0], np.cumsum([h.days_in_year(y) for y in range(1901, 1907)])])
+
+    def context(state, monthly, days):
+        ctx = h.Context(n, inp["zi"], nlayers=L, nisurf=inp["nisurf"], grow_on=inp.get("grow_on", True), nslots=3)
+        ctx.set_params(params)
+        ctx.set_evap(True)
+        ctx.set_monthly(monthly)
+        ctx.set_days(days)
+        ctx.init_state() if state is None else ctx.set_state(state)
+        return ctx
+
+    def run(ctx, years, ordered, monthly, days):
+        """Runs the years; the recorded (months, day records) of each."""
+        for k, y in enumerate(years):
+            ctx.push_forcing(k, inp["forcing"][:, d0[y - 1901]:d0[y - 1900], :n])
+        if ordered:
+            ctx.run_ordered(list(range(len(years))), years[0])
+        else:
+            ctx.run_year(0, years[0])
+            ctx.sync()
+        for get, on in ((ctx.get_monthly, monthly), (ctx.get_days, days)):
+            if on:
+                with pytest.raises(h.H9GError, match="failed with -1"):     # H9G_EINVAL
+                    get(len(years))
+        return ([ctx.get_monthly(k) for k in range(len(years))] if monthly else [],
+                [ctx.get_days(k) for k in range(len(years))] if days else [])
+
+    steps = (((1901, 1902), True, True, False),               # years, ordered, monthly, days
+             ((1903, 1904, 1905), True, True, True),
+             ((1906,), False, False, True))
+    with context(None, True, False) as reused:
+        for years, ordered, monthly, days in steps:
+            start = reused.get_state()
+            assert not reused.get_errors()["code"].any()       # (a fresh context's STOP records: none)
+            reused.set_monthly(monthly)
+            reused.set_days(days)
+            got = run(reused, years, ordered, monthly, days)
+            with context(start, monthly, days) as fresh:
+                want = run(fresh, years, ordered, monthly, days)
+                assert same_bits(reused.get_state(), fresh.get_state())
+            for g, w in zip(got, want):
+                assert len(g) == len(w) == (len(years) if len(w) else 0)
+                assert all(a.shape == b.shape and same_bits(a, b) for a, b in zip(g, w))
+            assert [d.shape[0] for d in got[1]] == [h.days_in_year(y) for y in years if days]
+        with pytest.raises(h.H9GError, match="nothing recorded"):
+            reused.get_monthly()
+        assert reused.get_days(0).shape == (365, ND, n)
+
+
+# ---- 11. the Fortran host ----------------------------------------------------------
 def test_fortran_host_writes_dxy(tmp_path):
     from tests.test_fortran_host import _build
     exe = _build()
