@@ -32,6 +32,15 @@ NDAYREC = 7              # H9G_NDAYREC: the day record (DAY_FIELDS)
 # The rows of a day record (Context.get_days); rnf_sum and evap_sum are the
 # year's running sums (day_values differences them).
 DAY_FIELDS = ("rnf_sum", "evap_sum", "soil_water", "theta1", "zwt", "wa", "LAI")
+NDAYSTAT = 17            # H9G_NDAYSTAT: the day statistics (DAYSTAT_FIELDS)
+# The rows of Context.get_daystats / day_stats, per cell and year.
+DAYSTAT_FIELDS = ("ndays", "q_max", "q_max_day", "q7_min", "q_days", "e_max", "w_min", "w_min_day", "w_max",
+                  "theta1_min", "dry_days", "dry_spell", "zwt_min", "wet_days", "lai_max", "lai_max_day",
+                  "green_days")
+# Thresholds of the counting rows where the caller names none: a runoff day has
+# q >= q_thr (mm/day), a dry day theta(1) < theta_thr (mm3/mm3), a wet day
+# zwt <= zwt_thr (mm), a green day LAI >= lai_thr.
+DAYSTAT_THRESHOLDS = dict(q_thr=1.0, theta_thr=0.2, zwt_thr=1000.0, lai_thr=1.0)
 ANNUAL_SCALARS = ("npp", "plant_mass", "rnf", "evap", "tas", "rlds", "rsds",
                   "huss", "ps", "pr", "rhs")
 DIAG_NAMES = ("cells", "rnf_sum", "theta_total_sum", "zwt_sum", "wa_sum",
@@ -77,6 +86,21 @@ class _SpinOpts(C.Structure):
     _fields_ = [("max_cycles", C.c_int32), ("min_cycles", C.c_int32), ("freeze", C.c_int32),
                 ("reserved", C.c_int32), ("tol_water", C.c_double), ("tol_zwt", C.c_double),
                 ("tol_plant", C.c_double)]
+
+
+class _StatOpts(C.Structure):
+    _fields_ = [("q_thr", C.c_float), ("theta_thr", C.c_float), ("zwt_thr", C.c_float), ("lai_thr", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+def daystat_opts(**thresholds) -> _StatOpts:
+    """The ``h9g_daystat_opts`` of Context.get_daystats: q_thr, theta_thr,
+    zwt_thr, lai_thr (DAYSTAT_THRESHOLDS where not given), as float32."""
+    bad = set(thresholds) - set(DAYSTAT_THRESHOLDS)
+    if bad:
+        raise TypeError(f"unknown day-statistics thresholds {sorted(bad)}: {sorted(DAYSTAT_THRESHOLDS)}")
+    t = dict(DAYSTAT_THRESHOLDS, **thresholds)
+    return _StatOpts(float(t["q_thr"]), float(t["theta_thr"]), float(t["zwt_thr"]), float(t["lai_thr"]))
 
 
 NSPIN = 6                # H9G_NSPIN: a cycle's history row
@@ -183,6 +207,11 @@ def lib() -> C.CDLL:
         "h9g_spin_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, C.POINTER(C.c_int32),
                                         C.POINTER(_SpinOpts), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         _DP]),
+        "h9g_get_daystats": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(_StatOpts), _DP]),
+        "h9g_last_daystat_ms": (C.c_float, [vp]),
+        "h9g_daystat_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.POINTER(_StatOpts), _DP]),
+        "h9g_write_sxy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _I64P, C.c_int, C.POINTER(_StatOpts),
+                                       _DP]),
         "h9g_host_expf": (C.c_float, [C.c_float]),
         "h9g_host_powf": (C.c_float, [C.c_float, C.c_float]),
     }
@@ -275,6 +304,24 @@ def spin_selftest(state_prev, state, L: int, k: int, *, err=None, device: int = 
                                  st.ctypes.data_as(_DP))
     _check(rc, "h9g_spin_selftest")
     return dict(list=lst[:int(st[NSPIN])].copy(), cell_cycle=cc, stats=st[:NSPIN].copy())
+
+
+def daystat_selftest(records, *, nseg: int = 0, device: int = 0, **thresholds) -> np.ndarray:
+    """Context.get_daystats on hand-made records (nday, 7, ncell), through the
+    same kernel, with no context and no year run (h9g_daystat_selftest) ->
+    (17, ncell) float64.  nseg = 0: the product's cut of the year into slices;
+    nseg > 0: that many slices (1 .. 16) through the same code."""
+    r = np.ascontiguousarray(records, dtype=np.float32)
+    if r.ndim != 3 or r.shape[1] != NDAYREC:
+        raise ValueError("daystat_selftest: records must be (nday, 7, ncell)")
+    out = np.empty((NDAYSTAT, r.shape[2]), dtype=np.float64)
+    o = daystat_opts(**thresholds)
+    rc = lib().h9g_daystat_selftest(int(device), r.shape[2], r.shape[0], int(nseg), _fp(r), C.byref(o),
+                                    out.ctypes.data_as(_DP))
+    if rc == -1:
+        raise ValueError("daystat_selftest: empty records, nseg outside 0 .. 16 or a NaN threshold")
+    _check(rc, "h9g_daystat_selftest")
+    return out
 
 
 class Context:
@@ -626,6 +673,29 @@ class Context:
         _check(rc, "h9g_get_days")
         return out
 
+    # -- day statistics: per-cell annual indices from the day records --------
+    def get_daystats(self, k0: int = 0, nk: int = 1, **thresholds) -> np.ndarray:
+        """The day statistics of years k0 .. k0+nk-1 (0-based) of the last
+        run_year (k0 = 0, nk = 1) or ordered call that recorded days: (nk, 17,
+        ncell) float64 in DAYSTAT_FIELDS' order, reduced on the device from the
+        day records where they lie (h9g_get_daystats; ``day_stats`` states the
+        definition).  thresholds: q_thr, theta_thr, zwt_thr, lai_thr
+        (DAYSTAT_THRESHOLDS).  Synchronises, as get_days does."""
+        o = daystat_opts(**thresholds)
+        out = np.empty((max(int(nk), 1), NDAYSTAT, self.ncell), dtype=np.float64)
+        rc = self._lib.h9g_get_daystats(self._h, int(k0), int(nk), C.byref(o), out.ctypes.data_as(_DP))
+        if rc == -4:
+            raise H9GError("h9g_get_daystats: nothing recorded (H9G_ESTATE): set_evap(), set_days(), then run")
+        if rc == -1:
+            raise ValueError("get_daystats: years outside those the last call recorded, or a NaN threshold "
+                             "(H9G_EINVAL)")
+        _check(rc, "h9g_get_daystats")
+        return out
+
+    def last_daystat_ms(self) -> float:
+        """Device time of the last get_daystats' launches (h9g_last_daystat_ms)."""
+        return float(self._lib.h9g_last_daystat_ms(self._h))
+
     def sync(self, raise_on_stop: bool = True) -> int:
         rc = _check(self._lib.h9g_sync(self._h), "h9g_sync")
         if rc and raise_on_stop:
@@ -771,6 +841,96 @@ def day_values(records) -> np.ndarray:
     return out
 
 
+def _first_extreme(v, largest: bool):
+    """Per column of v (nday, n): the largest (smallest) value that is not NaN
+    and the row of its first occurrence, as float64; (NaN, -1) with none."""
+    n = v.shape[1]
+    if v.shape[0] == 0:
+        return np.full(n, np.nan), np.full(n, -1.0)
+    ok = ~np.isnan(v)
+    key = np.where(ok, v, -np.inf if largest else np.inf)
+    i = key.argmax(axis=0) if largest else key.argmin(axis=0)     # (the first of equal values; -0 == +0)
+    # (every candidate an infinity of the padding's sign: the first candidate)
+    i = np.where(np.take_along_axis(ok, i[None], axis=0)[0], i, ok.argmax(axis=0))
+    some = ok.any(axis=0)
+    val = np.take_along_axis(v, i[None], axis=0)[0].astype(np.float64)
+    return np.where(some, val, np.nan), np.where(some, i, -1).astype(np.float64)
+
+
+def day_stats(records, **thresholds) -> np.ndarray:
+    """One year's day statistics from its day records (nday, 7, ncell)
+    (Context.get_days) -> (17, ncell) float64 in DAYSTAT_FIELDS' order: the
+    numpy statement of what Context.get_daystats computes on the device, bit
+    for bit.  With R the records, S = R[:, 0] in float64 and S[-1] = 0:
+    q[d] = S[d] - S[d-1] (the day's runoff, day_values' difference before its
+    rounding), e[d] the same from row 1, q7[d] = S[d] - S[d-7] for d >= 6.
+
+        ndays                  days none of whose seven values is NaN
+        q_max, q_max_day       largest q; 0-based day of its first occurrence
+        q7_min                 smallest q7
+        q_days                 days with q >= q_thr (in float64)
+        e_max                  largest e
+        w_min, w_min_day       smallest soil_water (row 2); first day
+        w_max                  largest soil_water
+        theta1_min             smallest theta1 (row 3)
+        dry_days               days with theta1 < theta_thr (in float32)
+        dry_spell              longest run of consecutive dry days
+        zwt_min                smallest zwt (row 4)
+        wet_days               days with zwt <= zwt_thr
+        lai_max, lai_max_day   largest LAI (row 6); first day
+        green_days             days with LAI >= lai_thr
+
+    A NaN is never a candidate and never counted (a STOP day and later, a
+    masked cell), and ends a dry run; with no candidate an extreme is NaN and
+    its day -1.  Of equal extremes the first day is kept.  thresholds: q_thr,
+    theta_thr, zwt_thr, lai_thr (DAYSTAT_THRESHOLDS), taken as float32.
+    Derived from the reference's f32 running sums: deterministic, but not a
+    reference quantity."""
+    r = np.asarray(records, dtype=np.float32)
+    if r.ndim != 3 or r.shape[1] != NDAYREC:
+        raise ValueError("day_stats: records must be (nday, 7, ncell)")
+    o = daystat_opts(**thresholds)
+    nt, _, n = r.shape
+    s = r[:, :2].astype(np.float64)
+    d = np.diff(s, axis=0, prepend=np.zeros_like(s[:1]))
+    q, e = d[:, 0], d[:, 1]
+    before = np.concatenate([np.zeros((1, n)), s[:-7, 0]]) if nt >= 7 else np.zeros((0, n))
+    q7 = s[6:, 0] - before
+    out = np.empty((NDAYSTAT, n), dtype=np.float64)
+    out[0] = (~np.isnan(r).any(axis=1)).sum(axis=0)
+    out[1], out[2] = _first_extreme(q, True)
+    out[3] = _first_extreme(q7, False)[0]
+    out[4] = (q >= np.float64(np.float32(o.q_thr))).sum(axis=0)
+    out[5] = _first_extreme(e, True)[0]
+    out[6], out[7] = _first_extreme(r[:, 2], False)
+    out[8] = _first_extreme(r[:, 2], True)[0]
+    out[9] = _first_extreme(r[:, 3], False)[0]
+    dry = r[:, 3] < np.float32(o.theta_thr)
+    out[10] = dry.sum(axis=0)
+    day1 = np.arange(1, nt + 1)[:, None]
+    run = np.where(dry, day1 - np.maximum.accumulate(np.where(dry, 0, day1), axis=0), 0)
+    out[11] = run.max(axis=0)
+    out[12] = _first_extreme(r[:, 4], False)[0]
+    out[13] = (r[:, 4] <= np.float32(o.zwt_thr)).sum(axis=0)
+    out[14], out[15] = _first_extreme(r[:, 6], True)
+    out[16] = (r[:, 6] >= np.float32(o.lai_thr)).sum(axis=0)
+    return out
+
+
+def write_sxy_nc(path, stats, gid, jyear: int, nx: int = 720, ny: int = 360, **thresholds):
+    """One year of day statistics (17, ncell) float64 (Context.get_daystats,
+    day_stats) of the cells gid to sxyYYYY.nc: 17 float64 variables named as
+    DAYSTAT_FIELDS on write_axy_nc's latitude / longitude grid, NaN fill, the
+    thresholds they were taken with as global attributes (h9g_write_sxy_nc;
+    netCDF classic, 64-bit offsets)."""
+    stats = np.ascontiguousarray(stats, dtype=np.float64)
+    gid = np.ascontiguousarray(gid, dtype=np.int64)
+    assert stats.shape == (NDAYSTAT, gid.size)
+    o = daystat_opts(**thresholds)
+    _check(lib().h9g_write_sxy_nc(str(path).encode(), nx, ny, gid.size, gid.ctypes.data_as(_I64P), int(jyear),
+                                  C.byref(o), stats.ctypes.data_as(_DP)), "h9g_write_sxy_nc")
+
+
 def write_dxy_nc(path, records, gid, zc, jyear: int, nx: int = 720, ny: int = 360):
     """One year of day records (nday, 7, ncell) of the cells gid, as
     ``day_values`` derives them, to dxyYYYY.nc: seven variables under a leading
@@ -828,7 +988,7 @@ def decades(year0: int, nyears: int):
 
 def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                    state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None,
-                   monthly=False, evap=False, days=False):
+                   monthly=False, evap=False, days=False, daystats: dict | None = None):
     """``run`` in the reference's own cell order (smp carried from cell to
     cell, cells in the given order; chains: a reference rank per cell, each
     rank its own chain, shard.reference_blocks).  pipelined: one
@@ -843,7 +1003,12 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
     stay overlapped.  evap: evapotranspiration recording (Context.set_evap):
     row evap of annual and monthly is the year's evaporation sum.  days: day
     records (Context.set_days; turns evap on) -> out["days"] (nyears, 366, 7,
-    n), day 366 of a 365-day year NaN; the decades stay overlapped."""
+    n), day 366 of a 365-day year NaN; the decades stay overlapped.  daystats:
+    dict of thresholds (may be empty; DAYSTAT_THRESHOLDS): the day statistics
+    (Context.get_daystats; turns evap and day recording on) ->
+    out["daystats"] (nyears, 17, n), one call over the years of an ordered
+    call; the records themselves are copied out only with days."""
+    want_days, days = days, days or daystats is not None
     evap = evap or days
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
@@ -880,15 +1045,18 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
                     out["daily"] = np.concatenate([ctx.get_daily(k) for k in range(nyears)])
                 if monthly:
                     out["monthly"] = np.stack([ctx.get_monthly(k) for k in range(nyears)])
-                if days:
+                if want_days:
                     out["days"] = _days_years(ctx, nyears)
+                if daystats is not None:
+                    out["daystats"] = ctx.get_daystats(0, nyears, **daystats)
                 return out
     if pipelined:
         # a STOP: the reference program ends in that decade, while run_ordered
         # goes on with the other cells; the decade-by-decade form stops there
         return run_cell_order(zi=zi, params=params, forcing=forcing, nisurf=nisurf, year0=year0, nyears=nyears,
                               grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False,
-                              daily_cells=daily_cells, monthly=monthly, evap=evap, days=days)
+                              daily_cells=daily_cells, monthly=monthly, evap=evap, days=want_days,
+                              daystats=daystats)
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device, nslots=10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
@@ -906,7 +1074,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             ctx.set_state(state0)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
-        rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if days else None
+        rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if want_days else None
+        stats = np.full((nyears, NDAYSTAT, n), np.nan, dtype=np.float64)
         d0, rc, err, passes, work, daily = 0, 0, None, [], [], []
         for y0, ny in decades(year0, nyears):
             for k in range(ny):
@@ -922,8 +1091,10 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             if monthly:
                 for k in range(ny):
                     mon[y0 - year0 + k] = ctx.get_monthly(k)
-            if days:
+            if want_days:
                 rec[y0 - year0:y0 - year0 + ny] = _days_years(ctx, ny)
+            if daystats is not None:
+                stats[y0 - year0:y0 - year0 + ny] = ctx.get_daystats(0, ny, **daystats)
             rc = ctx.decade_rc
             if rc:
                 err = ctx.last_error()
@@ -934,8 +1105,10 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             out["daily"] = np.concatenate(daily)
         if monthly:
             out["monthly"] = mon
-        if days:
+        if want_days:
             out["days"] = rec
+        if daystats is not None:
+            out["daystats"] = stats
         return out
 
 
@@ -950,7 +1123,7 @@ def _days_years(ctx, nyears: int) -> np.ndarray:
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
         state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False,
-        evap=False, spinup: dict | None = None, days=False):
+        evap=False, spinup: dict | None = None, days=False, daystats: dict | None = None):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -966,13 +1139,18 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     annual and monthly is the year's evaporation sum instead of the
     reference's zero.  days: day records (Context.set_days; turns evap on)
     -> out["days"] (nyears, 366, 7, n) in DAY_FIELDS' order, day 366 of a
-    365-day year NaN.  spinup: dict(years=Y, max_cycles=..., and the other
+    365-day year NaN.  daystats: dict of thresholds (may be empty;
+    DAYSTAT_THRESHOLDS): the day statistics of every year
+    (Context.get_daystats; turns evap and day recording on) ->
+    out["daystats"] (nyears, 17, n) in DAYSTAT_FIELDS' order; the records
+    themselves are copied out only with days.  spinup: dict(years=Y, max_cycles=..., and the other
     keywords of Context.spinup): the first Y years of ``forcing``, resident in
     Y slots, are cycled to equilibrium before the run proper (Context.spinup;
     nothing is recorded meanwhile) -> out["spinup"]; the years of the run
     proper are unchanged and start from the spun-up state.  A STOP during
     spin-up takes that cell out of the run and is reported in out["spinup"]
     (rc) and in ``errors``."""
+    want_days, days = days, days or daystats is not None
     evap = evap or days
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
@@ -1005,7 +1183,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             ctx.set_days(True)
         ann = np.full((nyears, 12 + L, n), np.nan, dtype=np.float32)
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
-        rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if days else None
+        rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if want_days else None
+        stats = np.full((nyears, NDAYSTAT, n), np.nan, dtype=np.float64)
         d0, rc, err, daily = 0, 0, None, []
         for y in range(nyears):
             nt = days_in_year(year0 + y)
@@ -1017,8 +1196,10 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                 daily.append(ctx.get_daily())
             if monthly:
                 mon[y] = ctx.get_monthly()
-            if days:
+            if want_days:
                 rec[y, :nt] = ctx.get_days()
+            if daystats is not None:
+                stats[y] = ctx.get_daystats(**daystats)[0]
             d0 += nt
             if rc:
                 err = ctx.last_error()
@@ -1029,8 +1210,10 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             out["daily"] = np.concatenate(daily)
         if monthly:
             out["monthly"] = mon
-        if days:
+        if want_days:
             out["days"] = rec
+        if daystats is not None:
+            out["daystats"] = stats
         if spun is not None:
             out["spinup"] = spun
         return out

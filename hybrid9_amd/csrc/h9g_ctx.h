@@ -2,8 +2,8 @@
 // the description of a recorded output (RecStream) and of a year launch
 // (YearSpec), and the few functions that cross units.
 // Included by h9g.hip (context, forcing, the year launch, recording),
-// h9g_ord.hip (the ordered mode), h9g_spin.hip (spin-up) and h9g_aux.hip (soil
-// build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
+// h9g_ord.hip (the ordered mode), h9g_spin.hip (spin-up), h9g_stat.hip (day
+// statistics) and h9g_aux.hip (soil build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
 // h9g_et.hip, h9g_day.hip, h9g_cols.hip) do not include it: a change here recompiles no
 // geometry-templated kernel.  Their launchers are declared in h9g_year.h.
 #pragma once
@@ -145,6 +145,7 @@ struct h9g_ctx {
   // annual and monthly rows is the year's evaporation sum.  No buffer of its own.
   int evap = 0;
   struct SpinBufs *spin = nullptr;   // h9g_spinup's buffers (h9g_spin.hip); null until its first call
+  struct StatBufs *stat = nullptr;   // h9g_get_daystats' result buffer (h9g_stat.hip); null until its first call
 };
 
 // One year launch (run_year_impl).
@@ -190,4 +191,6 @@ H9G_LOCAL int diag_launch(h9g_ctx *ctx);
 H9G_LOCAL void ord_free(h9g_ctx *ctx);
 // h9g_spin.hip
 H9G_LOCAL void spin_free(h9g_ctx *ctx);
+// h9g_stat.hip
+H9G_LOCAL void stat_free(h9g_ctx *ctx);
 }

@@ -619,6 +619,7 @@ struct WVar {
   std::vector<int> dims;
   std::vector<Att> atts;
   uint64_t nel = 0, begin = 0;
+  int type = NC_FLOAT;             // NC_FLOAT or NC_DOUBLE
 };
 
 struct Buf {
@@ -647,6 +648,19 @@ Att text_att(const char *name, const char *v) {
   a.be.assign(v, v + strlen(v));
   return a;
 }
+Att double_att(const char *name, double v) {
+  Att a{name, NC_DOUBLE, {}, 1};
+  uint64_t u;
+  memcpy(&u, &v, 8);
+  for (int i = 7; i >= 0; i--) a.be.push_back((unsigned char)(u >> (8 * i)));
+  return a;
+}
+Att int_att(const char *name, int32_t v) {
+  Att a{name, NC_INT, {}, 1};
+  const uint32_t u = (uint32_t)v;
+  a.be = {(unsigned char)(u >> 24), (unsigned char)(u >> 16), (unsigned char)(u >> 8), (unsigned char)u};
+  return a;
+}
 Att float_att(const char *name, float v) {
   Att a{name, NC_FLOAT, {}, 1};
   uint32_t u;
@@ -655,10 +669,28 @@ Att float_att(const char *name, float v) {
   return a;
 }
 
-// CDF-2 file with fixed-size float variables; data(v, out) fills v's values.
+// CDF-2 file with fixed-size float (or double: WVar::type) variables; data(v,
+// out) fills v's values (out points at doubles for a double variable).  gatts:
+// the global attributes.
 template <class F>
 int write_cdf2(const char *path, const std::vector<std::pair<std::string, uint32_t>> &dims,
-               std::vector<WVar> &vars, F data) {
+               std::vector<WVar> &vars, F data, const std::vector<Att> &gatts = {}) {
+  auto put_atts = [](Buf &h, const std::vector<Att> &atts) {
+    if (atts.empty()) {
+      h.u32(0);
+      h.u32(0);
+      return;
+    }
+    h.u32(TAG_ATT);
+    h.u32((uint32_t)atts.size());
+    for (auto &a : atts) {
+      h.name(a.name);
+      h.u32((uint32_t)a.type);
+      h.u32(a.nel);
+      h.b.insert(h.b.end(), a.be.begin(), a.be.end());
+      h.pad();
+    }
+  };
   auto header = [&]() {
     Buf h;
     h.b = {'C', 'D', 'F', 2};
@@ -669,30 +701,16 @@ int write_cdf2(const char *path, const std::vector<std::pair<std::string, uint32
       h.name(d.first);
       h.u32(d.second);
     }
-    h.u32(0);                                    // no global attributes
-    h.u32(0);
+    put_atts(h, gatts);
     h.u32(TAG_VAR);
     h.u32((uint32_t)vars.size());
     for (auto &v : vars) {
       h.name(v.name);
       h.u32((uint32_t)v.dims.size());
       for (int d : v.dims) h.u32((uint32_t)d);
-      if (v.atts.empty()) {
-        h.u32(0);
-        h.u32(0);
-      } else {
-        h.u32(TAG_ATT);
-        h.u32((uint32_t)v.atts.size());
-        for (auto &a : v.atts) {
-          h.name(a.name);
-          h.u32((uint32_t)a.type);
-          h.u32(a.nel);
-          h.b.insert(h.b.end(), a.be.begin(), a.be.end());
-          h.pad();
-        }
-      }
-      h.u32(NC_FLOAT);
-      const uint64_t vs = pad4(v.nel * 4);
+      put_atts(h, v.atts);
+      h.u32((uint32_t)v.type);
+      const uint64_t vs = pad4(v.nel * type_size(v.type));
       h.u32(vs > 0xffffffffu ? 0xffffffffu : (uint32_t)vs);
       h.u64(v.begin);
     }
@@ -702,19 +720,25 @@ int write_cdf2(const char *path, const std::vector<std::pair<std::string, uint32
   uint64_t off = h.b.size();
   for (auto &v : vars) {
     v.begin = off;
-    off += pad4(v.nel * 4);
+    off += pad4(v.nel * type_size(v.type));
   }
   h = header();
   FILE *f = fopen(path, "wb");
   if (!f) return H9G_EINVAL;
   bool ok = fwrite(h.b.data(), 1, h.b.size(), f) == h.b.size();
-  std::vector<float> tmp;
+  std::vector<double> tmp;                       // (aligned for either type)
   for (size_t k = 0; ok && k < vars.size(); k++) {
-    tmp.assign(vars[k].nel, 0.0f);
-    data(k, tmp.data());
-    uint32_t *u = (uint32_t *)tmp.data();
-    for (uint64_t i = 0; i < vars[k].nel; i++) u[i] = __builtin_bswap32(u[i]);
-    ok = fwrite(tmp.data(), 4, vars[k].nel, f) == vars[k].nel;
+    const bool dbl = vars[k].type == NC_DOUBLE;
+    tmp.assign(dbl ? vars[k].nel : (vars[k].nel + 1) / 2, 0.0);
+    data(k, (float *)tmp.data());
+    if (dbl) {
+      uint64_t *u = (uint64_t *)tmp.data();
+      for (uint64_t i = 0; i < vars[k].nel; i++) u[i] = __builtin_bswap64(u[i]);
+    } else {
+      uint32_t *u = (uint32_t *)tmp.data();
+      for (uint64_t i = 0; i < vars[k].nel; i++) u[i] = __builtin_bswap32(u[i]);
+    }
+    ok = fwrite(tmp.data(), dbl ? 8 : 4, vars[k].nel, f) == vars[k].nel;
   }
   ok = (fclose(f) == 0) && ok;
   return ok ? 0 : H9G_EINVAL;
@@ -906,6 +930,50 @@ int h9g_write_dxy_nc(const char *path, int nx, int ny, int nlayers, const float 
       }
     }
   });
+}
+
+// sxyYYYY.nc: one year of day statistics (h9g_get_daystats: (17, ncell)
+// doubles) of the cells `gid` as 17 float64 variables on axyYYYY.nc's latitude
+// / longitude grid; every other grid cell is the NaN fill.  The thresholds the
+// counts were taken with, and the year, are global attributes.
+int h9g_write_sxy_nc(const char *path, int nx, int ny, int ncell, const int64_t *gid, int jyear,
+                     const h9g_daystat_opts *opts, const double *stats) {
+  if (!path || nx <= 0 || ny <= 0 || ncell < 0 || !opts || (ncell && (!gid || !stats))) return H9G_EINVAL;
+  for (int c = 0; c < ncell; c++)
+    if (gid[c] < 0 || gid[c] >= (int64_t)nx * ny) return H9G_EINVAL;
+  const double nan = std::nan("");
+  const std::vector<std::pair<std::string, uint32_t>> dims = {{"latitude", (uint32_t)ny}, {"longitude", (uint32_t)nx}};
+  const char *days = "days", *doy = "day of year (0-based)";
+  struct F2 { const char *name, *units; };
+  const F2 f2[H9G_NDAYSTAT] = {{"ndays", days}, {"q_max", "mm/day"}, {"q_max_day", doy}, {"q7_min", "mm/7 days"},
+                               {"q_days", days}, {"e_max", "mm/day"}, {"w_min", "mm"}, {"w_min_day", doy},
+                               {"w_max", "mm"}, {"theta1_min", "mm^3/mm^3"}, {"dry_days", days},
+                               {"dry_spell", days}, {"zwt_min", "mm"}, {"wet_days", days}, {"lai_max", "m^2/m^2"},
+                               {"lai_max_day", doy}, {"green_days", days}};
+  const uint64_t plane = (uint64_t)nx * ny;
+  std::vector<WVar> vars;
+  vars.push_back({"latitude", {0}, {text_att("units", "degrees_north")}, (uint64_t)ny});
+  vars.push_back({"longitude", {1}, {text_att("units", "degrees_east")}, (uint64_t)nx});
+  for (const F2 &v : f2) {
+    vars.push_back({v.name, {0, 1}, {text_att("units", v.units), double_att("_FillValue", nan)}, plane});
+    vars.back().type = NC_DOUBLE;
+  }
+  const std::vector<Att> gatts = {int_att("year", jyear), float_att("q_thr", opts->q_thr),
+                                  float_att("theta_thr", opts->theta_thr), float_att("zwt_thr", opts->zwt_thr),
+                                  float_att("lai_thr", opts->lai_thr)};
+  const float dlon = 360.0f / (float)nx, dlat = 180.0f / (float)ny;
+  return write_cdf2(path, dims, vars, [&](size_t k, float *out) {
+    if (k == 0) {                                // as write_xy_nc
+      for (int y = 0; y < ny; y++) out[y] = (90.0f - 0.5f * dlat) - (float)y * dlat;
+    } else if (k == 1) {
+      for (int x = 0; x < nx; x++) out[x] = (-180.0f + 0.5f * dlon) + (float)x * dlon;
+    } else {
+      double *o = (double *)out;
+      for (uint64_t i = 0; i < plane; i++) o[i] = nan;
+      const double *row = stats + (k - 2) * (size_t)ncell;
+      for (int c = 0; c < ncell; c++) o[gid[c]] = row[c];
+    }
+  }, gatts);
 }
 
 // READ_PGF.f90 + READ_NET_CDF_3DR.f90 for the cells of a context: days

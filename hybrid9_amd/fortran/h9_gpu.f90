@@ -40,7 +40,55 @@ TYPE, BIND(C) :: h9g_spinup_opts
   REAL(C_DOUBLE) :: tol_water, tol_zwt, tol_plant
 END TYPE h9g_spinup_opts
 
+! h9g_get_daystats' thresholds (include/h9g.h): a runoff day has q >= q_thr
+! (mm/day), a dry day theta(1) < theta_thr, a wet day zwt <= zwt_thr (mm), a
+! green day LAI >= lai_thr; reserved = 0.
+INTEGER, PARAMETER :: H9G_NDAYSTAT = 17
+TYPE, BIND(C) :: h9g_daystat_opts
+  REAL(C_FLOAT) :: q_thr, theta_thr, zwt_thr, lai_thr
+  INTEGER(C_INT32_T) :: reserved (4)
+END TYPE h9g_daystat_opts
+
 INTERFACE
+  ! Day statistics of years k0 .. k0+nk-1 (0-based) of the last run that
+  ! recorded days, reduced on the device: out (ncell, 17, nk).
+  FUNCTION h9g_get_daystats (ctx, k0, nk, opts, out) BIND(C, NAME='h9g_get_daystats')
+    IMPORT :: C_PTR, C_INT, C_DOUBLE, h9g_daystat_opts
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: k0, nk
+    TYPE(h9g_daystat_opts), INTENT(IN) :: opts
+    REAL(C_DOUBLE), INTENT(OUT) :: out (*)
+    INTEGER(C_INT) :: h9g_get_daystats
+  END FUNCTION
+  ! Device ms of the last h9g_get_daystats' launches.
+  FUNCTION h9g_last_daystat_ms (ctx) BIND(C, NAME='h9g_last_daystat_ms')
+    IMPORT :: C_PTR, C_FLOAT
+    TYPE(C_PTR), VALUE :: ctx
+    REAL(C_FLOAT) :: h9g_last_daystat_ms
+  END FUNCTION
+  ! The same kernel on hand-made records (n, 7, nt), nseg slices a year
+  ! (0: the product's): out (n, 17).
+  FUNCTION h9g_daystat_selftest (device, n, nt, nseg, records, opts, out) &
+           BIND(C, NAME='h9g_daystat_selftest')
+    IMPORT :: C_INT, C_FLOAT, C_DOUBLE, h9g_daystat_opts
+    INTEGER(C_INT), VALUE :: device, n, nt, nseg
+    REAL(C_FLOAT), INTENT(IN) :: records (*)
+    TYPE(h9g_daystat_opts), INTENT(IN) :: opts
+    REAL(C_DOUBLE), INTENT(OUT) :: out (*)
+    INTEGER(C_INT) :: h9g_daystat_selftest
+  END FUNCTION
+  ! One year of day statistics (ncell, 17) to sxyYYYY.nc: 17 float64
+  ! variables on axyYYYY.nc's grid, the thresholds as global attributes.
+  FUNCTION h9g_write_sxy_nc (path, nx, ny, ncell, gid, jyear, opts, stats) &
+           BIND(C, NAME='h9g_write_sxy_nc')
+    IMPORT :: C_INT, C_CHAR, C_DOUBLE, C_INT64_T, h9g_daystat_opts
+    CHARACTER(KIND=C_CHAR), INTENT(IN) :: path (*)
+    INTEGER(C_INT), VALUE :: nx, ny, ncell, jyear
+    INTEGER(C_INT64_T), INTENT(IN) :: gid (*)
+    TYPE(h9g_daystat_opts), INTENT(IN) :: opts
+    REAL(C_DOUBLE), INTENT(IN) :: stats (*)
+    INTEGER(C_INT) :: h9g_write_sxy_nc
+  END FUNCTION
   ! Spin-up to equilibrium: years jyear0 .. jyear0+nyears-1 (isolated cells,
   ! the forcing of year jyear0+k resident in slots(k+1)) repeated until the
   ! cells settle; history (H9G_NSPIN, max_cycles).

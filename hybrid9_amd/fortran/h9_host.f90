@@ -62,6 +62,14 @@ PROGRAM H9_HOST
 ! settings and with or without monthly; it implies evap = 1.  The grid is
 ! mxyYYYY.nc's.
 !
+! daystats = 1 reduces every year's day records on the device to 17 numbers per
+! cell (h9g_get_daystats, DESIGN.md §7: the largest daily runoff and its day,
+! the lowest 7-day flow, the driest the column got, the longest dry spell, ...)
+! with the thresholds q_thr (mm/day), theta_thr, zwt_thr (mm) and lai_thr, and
+! writes each year's to <out_dir>/sxyYYYY.nc (h9g_write_sxy_nc) where
+! dxyYYYY.nc is written, in both cell_order settings; it implies days and evap.
+! The dxy file is then written only if days = 1 was set too.
+!
 ! spinup_cycles > 0 (0 = off, the default) spins the cold start of
 ! INIT.f90:707-811 up to equilibrium before the run proper (h9g_spinup,
 ! DESIGN.md §7): the run's first spinup_years years (default 1) are staged
@@ -98,13 +106,15 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 ! --- extension namelist ----------------------------------------------------
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
-INTEGER :: cell_order, ordered_decades, daily, monthly, evap, days
+INTEGER :: cell_order, ordered_decades, daily, monthly, evap, days, daystats
+REAL(C_FLOAT) :: q_thr, theta_thr, zwt_thr, lai_thr
 INTEGER :: spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze
 REAL(C_DOUBLE) :: spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 INTEGER(C_INT64_T) :: seed
 NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
                  cell_order, ordered_decades, daily, monthly, evap, days, &
+                 daystats, q_thr, theta_thr, zwt_thr, lai_thr, &
                  spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze, &
                  spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
@@ -146,6 +156,11 @@ REAL(C_FLOAT), ALLOCATABLE :: mon (:,:,:)
 REAL(C_FLOAT), ALLOCATABLE :: drec (:,:,:)
 INTEGER(C_INT64_T), ALLOCATABLE :: mgid (:)
 INTEGER :: mnx, mny
+! --- day statistics (h9g_get_daystats): a year's 17 rows; rec_days: day
+! recording is on (days or daystats) -----------------------------------------
+TYPE(h9g_daystat_opts) :: dopts
+REAL(C_DOUBLE), ALLOCATABLE :: dstat (:,:)
+INTEGER :: rec_days
 ! --- spin-up (h9g_spinup) ---------------------------------------------------
 TYPE(h9g_spinup_opts) :: sopts
 INTEGER(C_INT32_T) :: scycles
@@ -159,6 +174,7 @@ input_mode = 'synth'; case_dir = ''; out_dir = '.'; pgf_dir = '.'
 nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
 monthly = 0; evap = 0; days = 0
+daystats = 0; q_thr = 1.0; theta_thr = 0.2; zwt_thr = 1000.0; lai_thr = 1.0
 spinup_cycles = 0; spinup_years = 1; spinup_min_cycles = 1; spinup_freeze = 1
 spinup_tol_water = HUGE (1.0D0); spinup_tol_zwt = HUGE (1.0D0); spinup_tol_plant = HUGE (1.0D0)
 daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
@@ -392,17 +408,22 @@ IF (daily /= 0) THEN
                   &  theta_ma_1,  lai,  lai_litter, w_i, fT'
   END IF
 END IF
-IF (days /= 0) evap = 1
+rec_days = 0
+IF (days /= 0 .OR. daystats /= 0) rec_days = 1
+IF (rec_days /= 0) evap = 1
 IF (evap /= 0) CALL chk (h9g_set_evap (ctx, 1))
 IF (monthly /= 0) THEN
   CALL chk (h9g_set_monthly (ctx, 1))
   ALLOCATE (mon (ncell, 12 + L, H9G_NMONTHS))
 END IF
-IF (days /= 0) THEN
-  CALL chk (h9g_set_days (ctx, 1))
-  ALLOCATE (drec (ncell, H9G_NDAYREC, 366))
+IF (rec_days /= 0) CALL chk (h9g_set_days (ctx, 1))
+IF (days /= 0) ALLOCATE (drec (ncell, H9G_NDAYREC, 366))
+IF (daystats /= 0) THEN
+  dopts%q_thr = q_thr; dopts%theta_thr = theta_thr; dopts%zwt_thr = zwt_thr; dopts%lai_thr = lai_thr
+  dopts%reserved = 0
+  ALLOCATE (dstat (ncell, H9G_NDAYSTAT))
 END IF
-IF (monthly /= 0 .OR. days /= 0) THEN
+IF (monthly /= 0 .OR. rec_days /= 0) THEN
   ALLOCATE (mgid (ncell))
   IF (TRIM (input_mode) == 'case') THEN
     mnx = ncell; mny = 1
@@ -456,6 +477,7 @@ IF (cell_order /= 0) THEN
       CALL year_out (dsyr + k - 1)
       IF (monthly /= 0) CALL month_out (k - 1, dsyr + k - 1)
       IF (days /= 0) CALL days_out (k - 1, dsyr + k - 1)
+      IF (daystats /= 0) CALL stats_out (k - 1, dsyr + k - 1)
     END DO
     CALL h9g_check_stop (ctx, rc)
     WRITE (*,'(A,I5,A,I5,A,12I3)') ' years', dsyr, ' -', deyr, ' in cell order: passes per decade', &
@@ -475,6 +497,7 @@ DO iyr = 1, nyears
   CALL year_out (jyear)
   IF (monthly /= 0) CALL month_out (0, jyear)
   IF (days /= 0) CALL days_out (0, jyear)
+  IF (daystats /= 0) CALL stats_out (0, jyear)
   IF (daily /= 0) THEN                       ! flushed at the end of each reference decade
     CALL daily_year (0, jyear)
     IF (MODULO (jyear - 1900, 10) == 0 .OR. iyr == nyears) CALL daily_flush ()
@@ -539,6 +562,16 @@ CONTAINS
     CALL chk (h9g_write_dxy_nc (TRIM (out_dir)//'/dxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, L, zc, ncell, &
                                 mgid, y, n, drec))
   END SUBROUTINE days_out
+
+  ! The day statistics of year k (0-based) of the last run, calendar year y,
+  ! to <out_dir>/sxyYYYY.nc.
+  SUBROUTINE stats_out (k, y)
+    INTEGER, INTENT(IN) :: k, y
+    CALL chk (h9g_get_daystats (ctx, k, 1, dopts, dstat))
+    WRITE (ydate,'(I4)') y
+    CALL chk (h9g_write_sxy_nc (TRIM (out_dir)//'/sxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, ncell, mgid, y, &
+                                dopts, dstat))
+  END SUBROUTINE stats_out
 
   ! The daily lines of year k (0-based) of the last run, calendar year y,
   ! appended to the current decade's.

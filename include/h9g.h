@@ -367,6 +367,63 @@ int h9g_set_days(h9g_ctx *ctx, int on);
  * was recorded, H9G_EINVAL for a bad k. */
 int h9g_get_days(h9g_ctx *ctx, int k, float *out);
 
+/* --- day statistics: per-cell annual indices from the day records --------- */
+/* The day records are the only output finer than a month, and a year of them
+ * is max_days x 7 x ncell floats.  h9g_get_daystats reduces them on the
+ * device, over the day axis, where they lie: per cell and year H9G_NDAYSTAT
+ * numbers, out (nk, 17, ncell) doubles, cell fastest, for years k0 ..
+ * k0+nk-1 of what the last h9g_run_year (k0 = 0, nk = 1),
+ * h9g_run_decade_ordered or h9g_run_ordered call recorded.  Synchronises, as
+ * h9g_get_days does.  H9G_ESTATE if nothing was recorded; H9G_EINVAL for a bad
+ * span, a null pointer, a NaN threshold or a non-zero `reserved`.
+ *
+ * R[d][r] is the year's record (f32), d = 0 .. nt-1; S[d] = (double)R[d][0]
+ * with S[-1] = 0, and the same for row 1.  Each of
+ *   q[d]  = S[d] - S[d-1]     the day's runoff (h9g_write_dxy_nc's difference,
+ *                             before its rounding to f32), mm
+ *   e[d]  = the same from row 1, mm
+ *   q7[d] = S[d] - S[d-7]     for d = 6 .. nt-1, with S[-1] = 0 at d = 6, mm
+ * is one IEEE operation.  A candidate that is NaN is skipped (a STOP day and
+ * later, a masked cell); a day is valid when none of its seven values is NaN.
+ *   row 0      ndays                  valid days
+ *   row 1, 2   q_max, q_max_day       largest q[d]; 0-based day of its first occurrence
+ *   row 3      q7_min                 smallest q7[d]
+ *   row 4      q_days                 days with q[d] >= (double)q_thr
+ *   row 5      e_max                  largest e[d]
+ *   row 6, 7   w_min, w_min_day       smallest row 2; first day
+ *   row 8      w_max                  largest row 2
+ *   row 9      theta1_min             smallest row 3
+ *   row 10     dry_days               days with row 3 < theta_thr
+ *   row 11     dry_spell              longest run of consecutive dry days; a day that
+ *                                     is not dry, or is NaN, ends a run
+ *   row 12     zwt_min                smallest row 4 (shallowest table)
+ *   row 13     wet_days               days with row 4 <= zwt_thr
+ *   row 14, 15 lai_max, lai_max_day   largest row 6; first day
+ *   row 16     green_days             days with row 6 >= lai_thr
+ * Extremes are kept by a strict comparison in day order: a later equal value
+ * never replaces an earlier one, and the first candidate that is not NaN
+ * starts the extreme.  With no candidate an extreme is NaN, its day -1 and the
+ * counts 0.  Counts and day numbers are exact in a double.  There is no
+ * floating-point sum whose order matters: every row is exact and comparable
+ * bit for bit with a restatement in numpy (hybrid9_amd.day_stats).
+ * Nothing here is a reference quantity: like the days' amounts and the monthly
+ * means it is deterministic and derived from the reference's f32 running sums.
+ * One memory-bound kernel (h9g_daystat_kernel) reads the records where
+ * h9g_get_days reads them and never copies them; no year kernel and no run
+ * path changes.  Its only allocation is the nk x 17 x ncell doubles of the
+ * result, made by the first call, grown when needed and released with the
+ * context (not part of h9g_config_bytes).  Without a call nothing is added
+ * anywhere: no launch, allocation or synchronisation. */
+#define H9G_NDAYSTAT 17
+typedef struct {
+  float q_thr;      /* mm/day:   a "runoff day" has q[d] >= q_thr (compared in double) */
+  float theta_thr;  /* mm3/mm3:  a "dry day" has theta1[d] < theta_thr (f32 compare)  */
+  float zwt_thr;    /* mm:       a "wet day" has zwt[d] <= zwt_thr                    */
+  float lai_thr;    /*           a "green day" has LAI[d] >= lai_thr                  */
+  int32_t reserved[4];  /* 0 */
+} h9g_daystat_opts;
+int h9g_get_daystats(h9g_ctx *ctx, int k0, int nk, const h9g_daystat_opts *opts, double *out);
+
 /* --- spin-up to equilibrium: cycle a forcing period, retire settled cells - */
 /* The model cold-starts from INIT.f90:707-811, and the reference's only
  * answer is to repeat years (its LCLIM loop re-reads the site years
@@ -509,6 +566,13 @@ int h9g_write_mxy_nc_evap(const char *path, int nx, int ny, int nlayers,
 int h9g_write_dxy_nc(const char *path, int nx, int ny, int nlayers,
                      const float *zc, int ncell, const int64_t *gid, int jyear,
                      int nday, const float *records);
+/* sxyYYYY.nc: one year of day statistics (h9g_get_daystats, (17, ncell)
+ * doubles) of the cells gid as 17 float64 variables on axyYYYY.nc's latitude /
+ * longitude grid, named as the rows above, NaN _FillValue, units as
+ * attributes (counts in "days", day numbers in "day of year (0-based)"); the
+ * four thresholds and the year are global attributes.  CDF-2.  Host only. */
+int h9g_write_sxy_nc(const char *path, int nx, int ny, int ncell, const int64_t *gid, int jyear,
+                     const h9g_daystat_opts *opts, const double *stats);
 /* READ_PGF.f90 / READ_NET_CDF_3DR.f90: days [t0, t0+nt) of variable 4
  * (time, lat, lon) of the 7 PGF files (tas rlds rsds huss ps pr rhs)
  * gathered at the grid ids gid into out (7, nt, ncell).  Host only. */
@@ -563,6 +627,9 @@ const char *h9g_kernel_name(h9g_ctx *ctx);
  * the cell order's one-day probe launches (launches, cells, ms).  Returns
  * the count written (<= 21). */
 int h9g_launch_stats(h9g_ctx *ctx, double *out, int n, int reset);
+/* Device time (HIP events on the compute stream) of the launches of the last
+ * h9g_get_daystats; 0 before the first. */
+float h9g_last_daystat_ms(h9g_ctx *ctx);
 /* Digest of the sources and compile flags of this library (16 hex digits;
  * hybrid9_amd/build.py build_id).  Profiles record it, and the bench
  * attaches counters only to the build they were measured on.  No GPU. */
@@ -592,6 +659,13 @@ int h9g_div_selftest(int device, int n, const float *x, const float *d,
 int h9g_spin_selftest(int device, int n, int L, const float *state_prev, const float *state,
                       const int32_t *err, const h9g_spinup_opts *opts, int k,
                       int32_t *list, int32_t *cell_cycle, double *stats);
+/* h9g_get_daystats on hand-made records, through the same kernel, with no
+ * context and no year run: records (nt, 7, n) host, out (17, n).  nseg = 0 is
+ * the product's cut of the year into slices; nseg > 0 cuts it into that many
+ * (1 .. 16: the largest workgroup built) through the same code, so a test can
+ * show that the cut does not matter. */
+int h9g_daystat_selftest(int device, int n, int nt, int nseg, const float *records,
+                         const h9g_daystat_opts *opts, double *out);
 /* Hardware ids as the pair kernel's issue pacer decodes them: nblocks
  * workgroups of the pair kernel's shape and LDS size; per wave out[3w..3w+2]
  * = HW_REG_HW_ID, HW_REG_XCC_ID, 1 if every wave was resident at once. */
