@@ -15,8 +15,9 @@
 // Layer split: lane h (0 = even, 1 = odd) of a pair owns layers 2t+1+h,
 // t = 0..L/2-1.  A per-layer phase evaluates the reference expression for
 // the lane's own layers and swaps the results with the partner lane (DPP
-// quad_perm [1,0,3,2]); everything else (energy balance, tridiagonal
-// system, Thomas solve, drainage, ...) runs identically in both lanes.
+// quad_perm [1,0,3,2]); the tridiagonal system's interface fluxes are split
+// the same way, interface 2t+1+h on lane h (H9G_FLUX_SPLIT); everything
+// else (Thomas solve, drainage, ...) runs identically in both lanes.
 // Every value is computed by exactly the reference expression, so the
 // split changes no bit.
 //
@@ -113,6 +114,14 @@ static_assert((PS_DAY + D_NUMC) % 2 == 0 && (PS_DAY + D_RAARAC) % 2 == 0 && (PS_
 #if !H9G_P1_FRONT || (H9G_P1_TASKS & 3) != 3   // the chain's operands are round A's and round C's
 #undef H9G_P1_SIDE
 #define H9G_P1_SIDE 0
+#endif
+// The tridiagonal system's interface fluxes as a third pair-split phase
+// (hydrology_pair, "the interface fluxes, split"): lane h of a pair evaluates
+// interface 2t+1+h in slot t instead of both lanes evaluating all of them, in
+// every store with kFluxSplit.  0 builds every kernel with the block that both
+// lanes evaluate whole.
+#ifndef H9G_FLUX_SPLIT
+#define H9G_FLUX_SPLIT 1
 #endif
 enum : int { ROLE_ALL = 0, ROLE_FRONT = 1, ROLE_MAIN = 2, ROLE_CHAIN = 3, ROLE_MAINS = 4 };
 struct FrontRes {
@@ -213,6 +222,7 @@ H9K_HD float hi_d(double v) {
 template <int L>
 struct FlatStore {                     // host: one flat array per cell
   static constexpr bool kRecip = true, kRts = true, kDayRecip = true, kRtsHK = true, kSpare = false, kFront = false;
+  static constexpr bool kFluxSplit = true;           // the interface fluxes by pair parity (H9G_FLUX_SPLIT): the device pair kernels' text
   static constexpr int N = PF_N * L + PS_N;
   float *b;
   const float *zt;                     // zi(0..L+1), then zi(0..L+1)/1000
@@ -402,6 +412,9 @@ struct PairStore {
   // L = 10 build of 22-column waves, whose registers they push further into
   // scratch
   static constexpr bool kSpare = !(L >= 10 && R >= 3 && S >= 44);
+  // the interface fluxes split over the pair (H9G_FLUX_SPLIT); not in the
+  // one-column waves, whose round C has a lane per interface
+  static constexpr bool kFluxSplit = S > 2;
   __device__ __forceinline__ void day_start(int day) const { pace.day_start(day, RESIDENT); }
   __device__ __forceinline__ float zi(int i) const { return zt[i]; }
   __device__ __forceinline__ float zim(int i) const { return zt[L + 2 + i]; }
@@ -490,6 +503,7 @@ struct PairStore {
 template <int L, bool EV = false>
 struct SoloStore {
   static constexpr bool kRecip = false, kRts = false, kDayRecip = false, kRtsHK = false, kSpare = false, kFront = false;
+  static constexpr bool kFluxSplit = false;          // one lane per column: nothing to split
   static constexpr int NPF = PF_RPSI0 + 2;           // TS..ROOTR, SVH2O, SVSMP
   static constexpr int NPS = PS_LAI + 5 + (EV ? 1 : 0);   // FMAX..DAY, SV*
   static constexpr int ROWS = NPF * L + NPS;
@@ -679,6 +693,28 @@ struct Split2 {
     for (int t = 0; t < NT; t++) {
 #pragma unroll
       for (int k = 0; k < K; k++) xchg(r[t].v[k], out[k][2 * t + 1], out[k][2 * t + 2]);
+    }
+  }
+  // par_d that also leaves the lane's own results in r, and exchanges only the
+  // outputs k with bit k of XM set (the flux phase reads the others from the
+  // lane that holds them: hydrology_pair)
+  template <int NT, int K, unsigned XM, int FE = 1, class FF, class FX>
+  H9K_HD void par_k(FF fast, FX exact, float *const (&out)[K], FV<K> (&r)[NT]) const {
+    bool bad = false;
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      r[t] = fast(t, h, bad);
+      if ((t + 1) % FE == 0 || t == NT - 1) sched_fence();
+    }
+    if (__builtin_expect(bad, 0)) {
+#pragma unroll
+      for (int t = 0; t < NT; t++) r[t] = exact(t, h);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int k = 0; k < K; k++)
+        if ((XM >> k) & 1) xchg(r[t].v[k], out[k][2 * t + 1], out[k][2 * t + 2]);
     }
   }
   template <int K, class F>
@@ -1111,6 +1147,14 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
   // the single powers and the aquifer node (below); a one-column wave's task
   // rounds evaluate them with the per-layer phases and leave picks = false
   constexpr bool kTask = pair1_tasks<M, SP, CS>();
+  // the interface fluxes split over the pair (below): a pair lane keeps its own
+  // slots' zq (own_q) and hk, dhkdw, smp, dsmpdw (own_k) for them, and hk,
+  // dhkdw and dsmpdw, which nothing else on the fast path reads, are not
+  // exchanged (kOwnFlux)
+  constexpr bool kFluxSplit = H9G_FLUX_SPLIT && CS::kFluxSplit && !M::kExact && !kTask && !kChain;
+  constexpr bool kOwnFlux = kFluxSplit && SP::kSpare;
+  FV<1> own_q[NT];
+  FV<4> own_k[NT];
   FV<1> p0{{zero}}, p1{{zero}};               // lane 0's and lane 1's power
   FV<2> eA{{zero, zero}}, eS{{zero, zero}};
   bool picks = true, aq_task = false;
@@ -1615,7 +1659,10 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           for (int t = 0; t < NT; t++) r[t] = eq_exact(t, hh);
         }
 #pragma unroll
-        for (int t = 0; t < NT; t++) sp.xchg(r[t].v[0], zq[2 * t + 1], zq[2 * t + 2]);
+        for (int t = 0; t < NT; t++) {
+          sp.xchg(r[t].v[0], zq[2 * t + 1], zq[2 * t + 2]);
+          if constexpr (kOwnFlux) own_q[t] = r[t];
+        }
       }
       pr.mark(2);
       {
@@ -1674,10 +1721,17 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
           for (int t = 0; t < NT; t++) r[t] = hk_exact(t, hh);
         }
 #pragma unroll
-        for (int t = 0; t < NT; t++)
+        for (int t = 0; t < NT; t++) {
 #pragma unroll
-          for (int kk = 0; kk < 4; kk++) sp.xchg(r[t].v[kk], outk[kk][2 * t + 1], outk[kk][2 * t + 2]);
+          for (int kk = 0; kk < 4; kk++)
+            if (!kOwnFlux || kk == 2) sp.xchg(r[t].v[kk], outk[kk][2 * t + 1], outk[kk][2 * t + 2]);
+          if constexpr (kOwnFlux) own_k[t] = r[t];
+        }
       }
+    } else if constexpr (kOwnFlux) {
+      sp.template par_k<NT, 1, 1u>(eq_fast, eq_exact, outq, own_q);
+      pr.mark(2);
+      sp.template par_k<NT, 4, 4u>(hk_fast, hk_exact, outk, own_k);
     } else {
       // (round 3: the two phases' slots interleaved in one region, twice the
       // independent powers per region, spilled 225 VGPRs: 214.5 vs 208.9 ms)
@@ -1862,6 +1916,116 @@ H9K_HD int hydrology_pair(const G &g, CS cs, const SP &sp0, St<L> &s, float &rnf
         d2[i] = c_2[i];
       }
     }
+    if constexpr (kFluxSplit) {
+      // ---- the interface fluxes, split (H9G_FLUX_SPLIT): a third pair-split
+      // phase.  Lane h evaluates in slot t interface i = 2t+1+h, between its
+      // own layer i and the partner's layer i+1: the even lane 1, 3, .., L-1,
+      // the odd lane 2, 4, .., L-2 and in its last slot the aquifer interface
+      // L.  flux3_f's expressions on flux3_f's operands, so no bit changes:
+      //   hk, dhkdw, smp, dsmpdw, zq of layer i: the lane's own slot results,
+      //     kept from the two phases above (own_k, own_q);
+      //   smp, zq of layer i+1: from the exchanged arrays, which the state,
+      //     beta and the recharge read anyway, by a select on the parity
+      //     (smp1, zq(L+1) for the aquifer interface);
+      //   dsmpdw of layer i+1: the partner's slot t (even lane) or t+1 (odd
+      //     lane), by one select of what to send and one pair_swap per slot --
+      //     2 NT + 1 instructions against 3 NT for two broadcasts and a select
+      //     -- and dsmpdw1 for the aquifer interface;
+      //   den, rden: g.den, g.rden of the two candidate layers selected on the
+      //     parity (three selects per slot; constants, no LDS read); the aquifer
+      //     interface's zcA - zc(L) and its reciprocal under the wave-uniform
+      //     any_aq as before.  Without any_aq the odd lane's last slot runs on
+      //     a divisor of 1, raises no flag and yields the zeros of flux3_f's
+      //     caller; its flag counts only for a lane with aq.
+      // The moves run here, in converged flow (the spare lanes have returned:
+      // both lanes of every pair are active); a flagged lane redoes its own
+      // slots by div_fix on the operands it holds, before the exchange (par_d).
+      // One lane for every layer (SplitAll) runs both parities on the arrays.
+      float *const outf[3] = {qo, d1, d2};
+      float denA = one;
+      double rdenA = 1.0;
+      if (any_aq) {
+        denA = zcA - g.zc(L);
+        rdenA = recip64(denA);
+      }
+      float ds_n[NT];
+      if constexpr (kOwnFlux) {
+#pragma unroll
+        for (int t = 0; t < NT - 1; t++) ds_n[t] = pair_swap(sel(sp.h, own_k[t + 1].v[3], own_k[t].v[3]));
+        ds_n[NT - 1] = sel(sp.h, pair_swap(own_k[NT - 1].v[3]), dsmpdw1);
+      }
+#if defined(H9G_FORCE_RERUN)
+      // test builds: the flag in about one wave-substep of two, in turn on the
+      // even lanes, the odd lanes and both (each shape of the lane-local redo)
+      const uint32_t f_u = __builtin_bit_cast(uint32_t, lane_get(zwtmm, 0));
+      const int f_shape = (f_u & 1u) ? 0 : 1 + (int)((f_u >> 1) % 3u);
+#endif
+      auto fx_ops = [&](int t, int h, float (&x)[3], float &den, double &rden) __attribute__((always_inline)) {
+        const bool last = t == NT - 1;
+        const int i0 = 2 * t + 1;
+        float hki, dhk, smi, dsi, zqi, dsn;
+        if constexpr (kOwnFlux) {
+          hki = own_k[t].v[0];
+          dhk = own_k[t].v[1];
+          smi = own_k[t].v[2];
+          dsi = own_k[t].v[3];
+          zqi = own_q[t].v[0];
+          dsn = ds_n[t];
+        } else {
+          hki = sel(h, hk[i0], hk[i0 + 1]);
+          dhk = sel(h, dhkdw[i0], dhkdw[i0 + 1]);
+          smi = sel(h, smp[i0], smp[i0 + 1]);
+          dsi = sel(h, dsmpdw[i0], dsmpdw[i0 + 1]);
+          zqi = sel(h, zq[i0], zq[i0 + 1]);
+          dsn = sel(h, dsmpdw[i0 + 1], last ? dsmpdw1 : dsmpdw[last ? L : i0 + 2]);
+        }
+        const float smn = sel(h, smp[i0 + 1], last ? smp1 : smp[last ? L : i0 + 2]);
+        const float zqn = sel(h, zq[i0 + 1], zq[i0 + 2]);
+        den = sel(h, g.den(i0), last ? denA : g.den(last ? i0 : i0 + 1));
+        rden = seld(h, g.rden(i0), last ? rdenA : g.rden(last ? i0 : i0 + 1));
+        const float num = flux_num(smn, smi, zqn, zqi);
+        x[0] = flux_q(hki, num);
+        x[1] = flux_d1(hki, num, dsi, dhk);
+        x[2] = flux_d2(hki, num, dsn, dhk);
+      };
+      auto fx_fast = [&](int t, int h, bool &fbad) __attribute__((always_inline)) -> FV<3> {
+        float x[3], den;
+        double rden;
+        fx_ops(t, h, x, den, rden);
+        FV<3> r;
+        bool b = false;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          r.v[k] = m.div_d(x[k], den, rden);
+          b |= m.div_bad(r.v[k]);
+        }
+        if (t == NT - 1) {
+          b = b && (!h || aq);
+#pragma unroll
+          for (int k = 0; k < 3; k++) r.v[k] = (h && !any_aq) ? zero : r.v[k];
+        }
+        fbad |= b;
+#if defined(H9G_FORCE_RERUN)
+        fbad |= f_shape == 3 || f_shape == 1 + h;
+#endif
+        return r;
+      };
+      auto fx_exact = [&](int t, int h) __attribute__((always_inline)) -> FV<3> {
+        if (t == 0) H9G_BR(BR_TRIFLUX);
+        float x[3], den;
+        double rden;
+        fx_ops(t, h, x, den, rden);
+        FV<3> r;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          r.v[k] = m.div_d(x[k], den, rden);
+          m.div_fix(r.v[k], x[k], den);
+          if (t == NT - 1) r.v[k] = (h && !any_aq) ? zero : r.v[k];
+        }
+        return r;
+      };
+      sp.template par_d<NT, 3, NT>(fx_fast, fx_exact, outf);
+    } else
     if (!kTask || __builtin_expect(!flux_done, 0)) {
 #pragma unroll
     for (int i = 1; i <= L - 1; i++)
