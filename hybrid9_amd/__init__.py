@@ -103,6 +103,35 @@ def daystat_opts(**thresholds) -> _StatOpts:
     return _StatOpts(float(t["q_thr"]), float(t["theta_thr"]), float(t["zwt_thr"]), float(t["lai_thr"]))
 
 
+NQUANT_MAX = 16          # H9G_NQUANT_MAX: quantiles of one Context.get_dayquant call
+# The daily series Context.get_dayquant orders: the day's runoff and
+# evapotranspiration (differences of the running sums, as day_stats' q and e)
+# and rows 2..6 of the day record.
+DAYQUANT_SERIES = ("q", "e", "soil_water", "theta1", "zwt", "wa", "LAI")
+
+
+class _QuantOpts(C.Structure):
+    _fields_ = [("series", C.c_int32), ("nq", C.c_int32), ("pooled", C.c_int32), ("reserved", C.c_int32),
+                ("p", C.c_double * NQUANT_MAX)]
+
+
+def dayquant_opts(*, series, p, pooled=False) -> _QuantOpts:
+    """The ``h9g_dayquant_opts`` of Context.get_dayquant.  series: one of
+    DAYQUANT_SERIES or its index; p: 1 .. 16 probabilities in [0, 1], in any
+    order (hydrology's "Q95", the flow exceeded 95 % of the time, is p = 0.05)."""
+    if isinstance(series, str):
+        if series not in DAYQUANT_SERIES:
+            raise ValueError(f"unknown day-quantile series {series!r}: {DAYQUANT_SERIES}")
+        series = DAYQUANT_SERIES.index(series)
+    p = np.atleast_1d(np.asarray(p, dtype=np.float64))
+    if p.ndim != 1 or not 1 <= p.size <= NQUANT_MAX:
+        raise ValueError(f"day quantiles: 1 .. {NQUANT_MAX} probabilities")
+    o = _QuantOpts(int(series), int(p.size), int(pooled), 0)
+    for i, v in enumerate(p):
+        o.p[i] = float(v)
+    return o
+
+
 NSPIN = 6                # H9G_NSPIN: a cycle's history row
 SPIN_HISTORY = ("cells_run", "settled", "stopped", "max_d_water", "max_d_zwt", "max_d_plant")
 
@@ -212,6 +241,12 @@ def lib() -> C.CDLL:
         "h9g_daystat_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.POINTER(_StatOpts), _DP]),
         "h9g_write_sxy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _I64P, C.c_int, C.POINTER(_StatOpts),
                                        _DP]),
+        "h9g_get_dayquant": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(_QuantOpts), _DP]),
+        "h9g_last_dayquant_ms": (C.c_float, [vp]),
+        "h9g_dayquant_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _FP,
+                                            C.POINTER(_QuantOpts), _DP]),
+        "h9g_write_qxy_nc": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _I64P, C.c_int, C.c_int,
+                                       C.POINTER(_QuantOpts), _DP]),
         "h9g_host_expf": (C.c_float, [C.c_float]),
         "h9g_host_powf": (C.c_float, [C.c_float, C.c_float]),
     }
@@ -321,6 +356,37 @@ def daystat_selftest(records, *, nseg: int = 0, device: int = 0, **thresholds) -
     if rc == -1:
         raise ValueError("daystat_selftest: empty records, nseg outside 0 .. 16 or a NaN threshold")
     _check(rc, "h9g_daystat_selftest")
+    return out
+
+
+def _quant_years(records_by_year):
+    """A list of years' records (nday_y, 7, ncell) -> (list of float32 arrays, ncell)."""
+    yrs = [np.asarray(r, dtype=np.float32) for r in records_by_year]
+    if not yrs or any(r.ndim != 3 or r.shape[1] != NDAYREC or r.shape[0] < 1 or r.shape[2] != yrs[0].shape[2]
+                      for r in yrs):
+        raise ValueError("day quantiles: a list of years' records, each (nday, 7, ncell)")
+    return yrs, yrs[0].shape[2]
+
+
+def dayquant_selftest(records_by_year, *, series, p, pooled=False, nseg: int = 0, device: int = 0) -> np.ndarray:
+    """Context.get_dayquant on hand-made records, a list of years each (nday_y,
+    7, ncell), through the same kernel, with no context and no year run
+    (h9g_dayquant_selftest) -> (nres, 1 + 2 len(p), ncell) float64.  nseg = 0:
+    the product's cut of a year into slices; nseg > 0: that many slices
+    (1 .. 16) through the same code."""
+    yrs, n = _quant_years(records_by_year)
+    o = dayquant_opts(series=series, p=p, pooled=pooled)
+    nt = np.array([r.shape[0] for r in yrs], dtype=np.int32)
+    rec = np.full((len(yrs), int(nt.max()), NDAYREC, n), np.nan, dtype=np.float32)
+    for y, r in enumerate(yrs):
+        rec[y, :r.shape[0]] = r
+    out = np.empty((1 if pooled else len(yrs), 1 + 2 * o.nq, n), dtype=np.float64)
+    rc = lib().h9g_dayquant_selftest(int(device), n, len(yrs), nt.ctypes.data_as(C.POINTER(C.c_int32)), int(nseg),
+                                     _fp(rec), C.byref(o), out.ctypes.data_as(_DP))
+    if rc == -1:
+        raise ValueError("dayquant_selftest: nseg outside 0 .. 16, more than 512 years, or options that "
+                         "h9g_get_dayquant refuses (H9G_EINVAL)")
+    _check(rc, "h9g_dayquant_selftest")
     return out
 
 
@@ -696,6 +762,31 @@ class Context:
         """Device time of the last get_daystats' launches (h9g_last_daystat_ms)."""
         return float(self._lib.h9g_last_daystat_ms(self._h))
 
+    def get_dayquant(self, k0: int = 0, nk: int = 1, *, series, p, pooled: bool = False) -> np.ndarray:
+        """Order statistics of one daily series (DAYQUANT_SERIES) of years k0 ..
+        k0+nk-1 of what the last run_year (k0 = 0, nk = 1), run_decade_ordered
+        or run_ordered call recorded -> (nk, or 1 when pooled, 1 + 2 len(p),
+        ncell) float64: row 0 the number m of days that count, rows 1 + 2i and
+        2 + 2i the order statistics x_(j) and x_(min(j+1, m-1)) around p[i], j
+        = floor(p[i] (m - 1)); selected on the device from the day records where
+        they lie (h9g_get_dayquant; ``day_order_stats`` states the same in
+        numpy, bit for bit; ``day_quantiles`` interpolates).  pooled: one
+        result over all days of the span's years.  Synchronises, as get_days does."""
+        o = dayquant_opts(series=series, p=p, pooled=pooled)
+        out = np.empty((1 if pooled else max(int(nk), 1), 1 + 2 * o.nq, self.ncell), dtype=np.float64)
+        rc = self._lib.h9g_get_dayquant(self._h, int(k0), int(nk), C.byref(o), out.ctypes.data_as(_DP))
+        if rc == -4:
+            raise H9GError("h9g_get_dayquant: nothing recorded (H9G_ESTATE): set_evap(), set_days(), then run")
+        if rc == -1:
+            raise ValueError("get_dayquant: years outside those the last call recorded, a series outside 0 .. 6 or "
+                             "a probability outside [0, 1] (H9G_EINVAL)")
+        _check(rc, "h9g_get_dayquant")
+        return out
+
+    def last_dayquant_ms(self) -> float:
+        """Device time of the last get_dayquant's launches (h9g_last_dayquant_ms)."""
+        return float(self._lib.h9g_last_dayquant_ms(self._h))
+
     def sync(self, raise_on_stop: bool = True) -> int:
         rc = _check(self._lib.h9g_sync(self._h), "h9g_sync")
         if rc and raise_on_stop:
@@ -931,6 +1022,93 @@ def write_sxy_nc(path, stats, gid, jyear: int, nx: int = 720, ny: int = 360, **t
                                   C.byref(o), stats.ctypes.data_as(_DP)), "h9g_write_sxy_nc")
 
 
+def day_order_stats(records_by_year, *, series, p, pooled=False) -> np.ndarray:
+    """Order statistics of one daily series from day records, a list of years
+    each (nday_y, 7, ncell) (Context.get_days) -> (nres, 1 + 2 len(p), ncell)
+    float64, nres = 1 when pooled, else one result per year: the numpy statement
+    of what Context.get_dayquant selects on the device, bit for bit.
+
+    Candidates: for series q and e the day's amount, S[d] - S[d-1] in float64
+    with S the year's running sum (row 0 or 1) and S[-1] = 0 in every year (as
+    day_stats' q and e); for the other series the record's row widened to
+    float64.  A NaN is no candidate; m candidates are left (row 0).  They are
+    ordered by their bits (the sign-magnitude pattern mapped to a monotone
+    unsigned key, so -0 comes before +0; np.sort on the floats would leave
+    those two in any order): x_(0) <= ... <= x_(m-1).  For p[i], g = p[i] *
+    float64(m - 1) and j = floor(g): row 1 + 2i is x_(j), row 2 + 2i is
+    x_(min(j + 1, m - 1)); both NaN where m = 0.  ``day_quantiles``
+    interpolates between the two."""
+    yrs, n = _quant_years(records_by_year)
+    o = dayquant_opts(series=series, p=p, pooled=pooled)
+    top = np.uint64(1) << np.uint64(63)
+    keys = []
+    for r in yrs:
+        x = r[:, o.series].astype(np.float64)
+        if o.series < 2:
+            with np.errstate(invalid="ignore"):                   # (inf - inf: a NaN, no candidate)
+                x = np.diff(x, axis=0, prepend=np.zeros_like(x[:1]))
+        u = np.ascontiguousarray(x).view(np.uint64)
+        k = u ^ np.where(u >> np.uint64(63) != 0, ~np.uint64(0), top)
+        keys.append(np.where(np.isnan(x), ~np.uint64(0), k))      # (no candidate has that key: it is a NaN's)
+    groups = [np.concatenate(keys)] if o.pooled else keys
+    out = np.empty((len(groups), 1 + 2 * o.nq, n), dtype=np.float64)
+    for res, k in enumerate(groups):
+        m = (k != ~np.uint64(0)).sum(axis=0)
+        ks = np.sort(k, axis=0)                                   # unsigned order: the candidates first
+        out[res, 0] = m
+        last = np.maximum(m, 1) - 1
+        for i in range(o.nq):
+            g = np.float64(o.p[i]) * last.astype(np.float64)
+            j = np.floor(g).astype(np.int64)
+            for row, idx in ((1 + 2 * i, j), (2 + 2 * i, np.minimum(j + 1, last))):
+                kk = np.take_along_axis(ks, idx[None], axis=0)[0]
+                u = kk ^ np.where(kk >> np.uint64(63) != 0, top, ~np.uint64(0))
+                out[res, row] = np.where(m > 0, u.view(np.float64), np.nan)
+    return out
+
+
+def day_quantiles(quant, p) -> np.ndarray:
+    """The quantiles of Context.get_dayquant's / day_order_stats' result
+    (..., 1 + 2 len(p), ncell) -> (..., len(p), ncell) float64: with m = row 0,
+    g = p[i] * float64(m - 1) and j = floor(g), lo + (hi - lo) * (g - j) in
+    float64 between the two order statistics (numpy's default "linear"
+    quantile); where they are equal, or g is whole, the lower one itself (an
+    infinite value does not turn into NaN).  Deterministic and derived, like
+    the monthly means."""
+    q = np.asarray(quant, dtype=np.float64)
+    p = np.atleast_1d(np.asarray(p, dtype=np.float64))
+    if q.shape[-2] != 1 + 2 * p.size:
+        raise ValueError("day_quantiles: quant must be (..., 1 + 2 len(p), ncell)")
+    m = q[..., 0, :]
+    out = np.empty(q.shape[:-2] + (p.size, q.shape[-1]), dtype=np.float64)
+    for i in range(p.size):
+        g = p[i] * (np.maximum(m, 1.0) - 1.0)
+        t = g - np.floor(g)
+        lo, hi = q[..., 1 + 2 * i, :], q[..., 2 + 2 * i, :]
+        with np.errstate(invalid="ignore"):
+            v = lo + (hi - lo) * t
+        out[..., i, :] = np.where((t == 0.0) | (lo == hi), lo, v)
+    return out
+
+
+def write_qxy_nc(path, quant, gid, year_first: int, year_last: int | None = None, nx: int = 720, ny: int = 360, *,
+                 series, p, pooled=False):
+    """One result of Context.get_dayquant / day_order_stats, (1 + 2 len(p),
+    ncell) float64, of the cells gid to qxyYYYY.nc (or qxyYYYY_YYYY.nc for a
+    pooled span): dimension quantile with coordinate p, count(lat, lon), and
+    lower, upper, value(quantile, lat, lon) -- value is day_quantiles'
+    interpolation -- float64 with NaN fill on write_axy_nc's latitude /
+    longitude grid; the series' name and the years are global attributes
+    (h9g_write_qxy_nc; netCDF classic, 64-bit offsets)."""
+    o = dayquant_opts(series=series, p=p, pooled=pooled)
+    quant = np.ascontiguousarray(quant, dtype=np.float64)
+    gid = np.ascontiguousarray(gid, dtype=np.int64)
+    assert quant.shape == (1 + 2 * o.nq, gid.size)
+    _check(lib().h9g_write_qxy_nc(str(path).encode(), nx, ny, gid.size, gid.ctypes.data_as(_I64P), int(year_first),
+                                  int(year_first if year_last is None else year_last), C.byref(o),
+                                  quant.ctypes.data_as(_DP)), "h9g_write_qxy_nc")
+
+
 def write_dxy_nc(path, records, gid, zc, jyear: int, nx: int = 720, ny: int = 360):
     """One year of day records (nday, 7, ncell) of the cells gid, as
     ``day_values`` derives them, to dxyYYYY.nc: seven variables under a leading
@@ -988,7 +1166,8 @@ def decades(year0: int, nyears: int):
 
 def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                    state0: np.ndarray | None = None, device=0, chains=None, pipelined=True, daily_cells=None,
-                   monthly=False, evap=False, days=False, daystats: dict | None = None):
+                   monthly=False, evap=False, days=False, daystats: dict | None = None,
+                   dayquant: dict | None = None):
     """``run`` in the reference's own cell order (smp carried from cell to
     cell, cells in the given order; chains: a reference rank per cell, each
     rank its own chain, shard.reference_blocks).  pipelined: one
@@ -1007,8 +1186,12 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
     dict of thresholds (may be empty; DAYSTAT_THRESHOLDS): the day statistics
     (Context.get_daystats; turns evap and day recording on) ->
     out["daystats"] (nyears, 17, n), one call over the years of an ordered
-    call; the records themselves are copied out only with days."""
-    want_days, days = days, days or daystats is not None
+    call; the records themselves are copied out only with days.  dayquant:
+    dict(series=, p=, pooled=False), the keywords of Context.get_dayquant (turns
+    evap and day recording on) -> out["dayquant"], one call over the years of
+    an ordered call: (nyears, 1 + 2 len(p), n), or with pooled (1, ...) over the
+    whole span (decade by decade: one result per decade)."""
+    want_days, days = days, days or daystats is not None or dayquant is not None
     evap = evap or days
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
@@ -1049,6 +1232,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
                     out["days"] = _days_years(ctx, nyears)
                 if daystats is not None:
                     out["daystats"] = ctx.get_daystats(0, nyears, **daystats)
+                if dayquant is not None:
+                    out["dayquant"] = ctx.get_dayquant(0, nyears, **dayquant)
                 return out
     if pipelined:
         # a STOP: the reference program ends in that decade, while run_ordered
@@ -1056,7 +1241,7 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
         return run_cell_order(zi=zi, params=params, forcing=forcing, nisurf=nisurf, year0=year0, nyears=nyears,
                               grow_on=grow_on, state0=state0, device=device, chains=chains, pipelined=False,
                               daily_cells=daily_cells, monthly=monthly, evap=evap, days=want_days,
-                              daystats=daystats)
+                              daystats=daystats, dayquant=dayquant)
     with Context(n, zi, nlayers=L, nisurf=nisurf, grow_on=grow_on, device=device, nslots=10) as ctx:
         ctx.set_chains(chains)
         ctx.set_params(params)
@@ -1076,7 +1261,7 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
         rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if want_days else None
         stats = np.full((nyears, NDAYSTAT, n), np.nan, dtype=np.float64)
-        d0, rc, err, passes, work, daily = 0, 0, None, [], [], []
+        d0, rc, err, passes, work, daily, quant = 0, 0, None, [], [], [], []
         for y0, ny in decades(year0, nyears):
             for k in range(ny):
                 nt = days_in_year(y0 + k)
@@ -1095,6 +1280,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
                 rec[y0 - year0:y0 - year0 + ny] = _days_years(ctx, ny)
             if daystats is not None:
                 stats[y0 - year0:y0 - year0 + ny] = ctx.get_daystats(0, ny, **daystats)
+            if dayquant is not None:
+                quant.append(ctx.get_dayquant(0, ny, **dayquant))
             rc = ctx.decade_rc
             if rc:
                 err = ctx.last_error()
@@ -1109,6 +1296,8 @@ def run_cell_order(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow
             out["days"] = rec
         if daystats is not None:
             out["daystats"] = stats
+        if dayquant is not None:
+            out["dayquant"] = np.concatenate(quant)
         return out
 
 
@@ -1123,7 +1312,8 @@ def _days_years(ctx, nyears: int) -> np.ndarray:
 
 def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
         state0: np.ndarray | None = None, device=0, stop_on_error=True, daily_cells=None, monthly=False,
-        evap=False, spinup: dict | None = None, days=False, daystats: dict | None = None):
+        evap=False, spinup: dict | None = None, days=False, daystats: dict | None = None,
+        dayquant: dict | None = None):
     """Run ``nyears`` years from ``year0`` for every cell (HYBRID9.f90:120-290).
 
     Same contract as ``oracle.port.run`` / ``oracle.refcase.run_case``:
@@ -1143,14 +1333,20 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
     DAYSTAT_THRESHOLDS): the day statistics of every year
     (Context.get_daystats; turns evap and day recording on) ->
     out["daystats"] (nyears, 17, n) in DAYSTAT_FIELDS' order; the records
-    themselves are copied out only with days.  spinup: dict(years=Y, max_cycles=..., and the other
+    themselves are copied out only with days.  dayquant: dict(series=, p=), the
+    keywords of Context.get_dayquant (turns evap and day recording on) ->
+    out["dayquant"] (nyears, 1 + 2 len(p), n); pooled is a ValueError here, since
+    an isolated run retains one year.  spinup: dict(years=Y, max_cycles=..., and the other
     keywords of Context.spinup): the first Y years of ``forcing``, resident in
     Y slots, are cycled to equilibrium before the run proper (Context.spinup;
     nothing is recorded meanwhile) -> out["spinup"]; the years of the run
     proper are unchanged and start from the spun-up state.  A STOP during
     spin-up takes that cell out of the run and is reported in out["spinup"]
     (rc) and in ``errors``."""
-    want_days, days = days, days or daystats is not None
+    if dayquant is not None and dayquant.get("pooled"):
+        raise ValueError("run: pooled day quantiles need an ordered call (run_cell_order); an isolated run "
+                         "retains one year")
+    want_days, days = days, days or daystats is not None or dayquant is not None
     evap = evap or days
     L = params["theta_s"].shape[1]
     n = params["fmax"].size
@@ -1185,6 +1381,7 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
         mon = np.full((nyears, NMONTHS, 12 + L, n), np.nan, dtype=np.float32)
         rec = np.full((nyears, 366, NDAYREC, n), np.nan, dtype=np.float32) if want_days else None
         stats = np.full((nyears, NDAYSTAT, n), np.nan, dtype=np.float64)
+        quant = [] if dayquant is None else np.full((nyears, 1 + 2 * dayquant_opts(**dayquant).nq, n), np.nan)
         d0, rc, err, daily = 0, 0, None, []
         for y in range(nyears):
             nt = days_in_year(year0 + y)
@@ -1200,6 +1397,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
                 rec[y, :nt] = ctx.get_days()
             if daystats is not None:
                 stats[y] = ctx.get_daystats(**daystats)[0]
+            if dayquant is not None:
+                quant[y] = ctx.get_dayquant(**dayquant)[0]
             d0 += nt
             if rc:
                 err = ctx.last_error()
@@ -1214,6 +1413,8 @@ def run(*, zi, params, forcing, nisurf=48, year0=1901, nyears=1, grow_on=True,
             out["days"] = rec
         if daystats is not None:
             out["daystats"] = stats
+        if dayquant is not None:
+            out["dayquant"] = quant
         if spun is not None:
             out["spinup"] = spun
         return out

@@ -26,6 +26,7 @@ UNITS = [
     (CSRC / "h9g_ord.hip", []),     # host runtime: the ordered mode and its small kernels
     (CSRC / "h9g_spin.hip", []),    # host runtime: spin-up to equilibrium and its kernel
     (CSRC / "h9g_stat.hip", []),    # host runtime: day statistics from the day records and their kernel
+    (CSRC / "h9g_quant.hip", []),   # host runtime: day quantiles from the day records and their kernel
     (CSRC / "h9g_aux.hip", []),     # soil build, synthetic inputs, self-tests
     (CSRC / "h9g_plain.hip", []),   # the plain year kernels (h9g_year.h)
     (CSRC / "h9g_mon.hip", []),     # the monthly kernels: the same kernels with the Months policy

@@ -220,6 +220,7 @@ void h9g_destroy(h9g_ctx *ctx) {
   ord_free(ctx);
   spin_free(ctx);
   stat_free(ctx);
+  quant_free(ctx);
   for (auto e : ctx->ev_copied) hipEventDestroy(e);
   for (auto e : ctx->ev_consumed) hipEventDestroy(e);
   for (int i = 0; i < NEVT; i++) {

@@ -3,7 +3,7 @@
 // (YearSpec), and the few functions that cross units.
 // Included by h9g.hip (context, forcing, the year launch, recording),
 // h9g_ord.hip (the ordered mode), h9g_spin.hip (spin-up), h9g_stat.hip (day
-// statistics) and h9g_aux.hip (soil build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
+// statistics), h9g_quant.hip (day quantiles) and h9g_aux.hip (soil build, synthetic inputs, self-tests).  The kernel units (h9g_plain.hip, h9g_mon.hip,
 // h9g_et.hip, h9g_day.hip, h9g_cols.hip) do not include it: a change here recompiles no
 // geometry-templated kernel.  Their launchers are declared in h9g_year.h.
 #pragma once
@@ -146,6 +146,7 @@ struct h9g_ctx {
   int evap = 0;
   struct SpinBufs *spin = nullptr;   // h9g_spinup's buffers (h9g_spin.hip); null until its first call
   struct StatBufs *stat = nullptr;   // h9g_get_daystats' result buffer (h9g_stat.hip); null until its first call
+  struct QuantBufs *quant = nullptr; // h9g_get_dayquant's result buffer (h9g_quant.hip); null until its first call
 };
 
 // One year launch (run_year_impl).
@@ -193,4 +194,6 @@ H9G_LOCAL void ord_free(h9g_ctx *ctx);
 H9G_LOCAL void spin_free(h9g_ctx *ctx);
 // h9g_stat.hip
 H9G_LOCAL void stat_free(h9g_ctx *ctx);
+// h9g_quant.hip
+H9G_LOCAL void quant_free(h9g_ctx *ctx);
 }

@@ -976,6 +976,69 @@ int h9g_write_sxy_nc(const char *path, int nx, int ny, int ncell, const int64_t 
   }, gatts);
 }
 
+// qxyYYYY.nc: one result of h9g_get_dayquant ((1 + 2 nq, ncell) doubles) of
+// the cells `gid` on axyYYYY.nc's latitude / longitude grid: the coordinate p
+// of dimension quantile, the count, and per quantile the two order statistics
+// and the value interpolated between them in double (the lower one where they
+// are equal or the rank is whole); every other grid cell is the NaN fill.
+int h9g_write_qxy_nc(const char *path, int nx, int ny, int ncell, const int64_t *gid, int year_first, int year_last,
+                     const h9g_dayquant_opts *opts, const double *quant) {
+  if (!path || nx <= 0 || ny <= 0 || ncell < 0 || !opts || opts->series < 0 || opts->series >= H9G_NDAYREC ||
+      opts->nq < 1 || opts->nq > H9G_NQUANT_MAX || year_last < year_first || (ncell && (!gid || !quant)))
+    return H9G_EINVAL;
+  for (int c = 0; c < ncell; c++)
+    if (gid[c] < 0 || gid[c] >= (int64_t)nx * ny) return H9G_EINVAL;
+  const double nan = std::nan("");
+  const int nq = opts->nq;
+  const std::vector<std::pair<std::string, uint32_t>> dims = {{"quantile", (uint32_t)nq},
+                                                              {"latitude", (uint32_t)ny},
+                                                              {"longitude", (uint32_t)nx}};
+  static const char *const series[H9G_NDAYREC] = {"q", "e", "soil_water", "theta1", "zwt", "wa", "LAI"};
+  static const char *const units[H9G_NDAYREC] = {"mm/day", "mm/day", "mm", "mm^3/mm^3", "mm", "mm", "m^2/m^2"};
+  const uint64_t plane = (uint64_t)nx * ny;
+  std::vector<WVar> vars;
+  vars.push_back({"latitude", {1}, {text_att("units", "degrees_north")}, (uint64_t)ny});
+  vars.push_back({"longitude", {2}, {text_att("units", "degrees_east")}, (uint64_t)nx});
+  vars.push_back({"p", {0}, {text_att("units", "1")}, (uint64_t)nq});
+  vars.back().type = NC_DOUBLE;
+  vars.push_back({"count", {1, 2}, {text_att("units", "days"), double_att("_FillValue", nan)}, plane});
+  vars.back().type = NC_DOUBLE;
+  for (const char *name : {"lower", "upper", "value"}) {
+    vars.push_back({name, {0, 1, 2}, {text_att("units", units[opts->series]), double_att("_FillValue", nan)},
+                    plane * nq});
+    vars.back().type = NC_DOUBLE;
+  }
+  const std::vector<Att> gatts = {text_att("series", series[opts->series]), int_att("year_first", year_first),
+                                  int_att("year_last", year_last), int_att("pooled", opts->pooled)};
+  const float dlon = 360.0f / (float)nx, dlat = 180.0f / (float)ny;
+  return write_cdf2(path, dims, vars, [&](size_t k, float *out) {
+    double *o = (double *)out;
+    if (k == 0) {                                // as write_xy_nc
+      for (int y = 0; y < ny; y++) out[y] = (90.0f - 0.5f * dlat) - (float)y * dlat;
+    } else if (k == 1) {
+      for (int x = 0; x < nx; x++) out[x] = (-180.0f + 0.5f * dlon) + (float)x * dlon;
+    } else if (k == 2) {
+      for (int i = 0; i < nq; i++) o[i] = opts->p[i];
+    } else if (k == 3) {
+      for (uint64_t i = 0; i < plane; i++) o[i] = nan;
+      for (int c = 0; c < ncell; c++) o[gid[c]] = quant[c];
+    } else {                                     // 4: lower, 5: upper, 6: value
+      for (uint64_t i = 0; i < plane * nq; i++) o[i] = nan;
+      for (int i = 0; i < nq; i++)
+        for (int c = 0; c < ncell; c++) {
+          const double m = quant[c], lo = quant[(size_t)(1 + 2 * i) * ncell + c],
+                       hi = quant[(size_t)(2 + 2 * i) * ncell + c];
+          double v = k == 4 ? lo : hi;
+          if (k == 6) {
+            const double g = opts->p[i] * ((m > 1.0 ? m : 1.0) - 1.0), t = g - std::floor(g);
+            v = (t == 0.0 || lo == hi) ? lo : lo + (hi - lo) * t;
+          }
+          o[(uint64_t)i * plane + gid[c]] = v;
+        }
+    }
+  }, gatts);
+}
+
 // READ_PGF.f90 + READ_NET_CDF_3DR.f90 for the cells of a context: days
 // [t0, t0+nt) of the 7 files (READ_PGF order tas rlds rsds huss ps pr rhs),
 // variable 4 of each (dims time, lat, lon), gathered at the grid ids gid

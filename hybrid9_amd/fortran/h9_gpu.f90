@@ -49,6 +49,15 @@ TYPE, BIND(C) :: h9g_daystat_opts
   INTEGER(C_INT32_T) :: reserved (4)
 END TYPE h9g_daystat_opts
 
+! h9g_get_dayquant's options (include/h9g.h): series 0: q, 1: e, 2..6: record
+! rows 2..6; nq probabilities p in [0, 1] (hydrology's Q95 is p = 0.05);
+! pooled = 1: one result over all years of the span; reserved = 0.
+INTEGER, PARAMETER :: H9G_NQUANT_MAX = 16
+TYPE, BIND(C) :: h9g_dayquant_opts
+  INTEGER(C_INT32_T) :: series, nq, pooled, reserved
+  REAL(C_DOUBLE) :: p (H9G_NQUANT_MAX)
+END TYPE h9g_dayquant_opts
+
 INTERFACE
   ! Day statistics of years k0 .. k0+nk-1 (0-based) of the last run that
   ! recorded days, reduced on the device: out (ncell, 17, nk).
@@ -88,6 +97,48 @@ INTERFACE
     TYPE(h9g_daystat_opts), INTENT(IN) :: opts
     REAL(C_DOUBLE), INTENT(IN) :: stats (*)
     INTEGER(C_INT) :: h9g_write_sxy_nc
+  END FUNCTION
+  ! Order statistics of one daily series of years k0 .. k0+nk-1 (0-based) of
+  ! the last run that recorded days, selected on the device: out (ncell,
+  ! 1 + 2 nq, nres), nres = 1 when opts%pooled = 1, else nk.
+  FUNCTION h9g_get_dayquant (ctx, k0, nk, opts, out) BIND(C, NAME='h9g_get_dayquant')
+    IMPORT :: C_PTR, C_INT, C_DOUBLE, h9g_dayquant_opts
+    TYPE(C_PTR), VALUE :: ctx
+    INTEGER(C_INT), VALUE :: k0, nk
+    TYPE(h9g_dayquant_opts), INTENT(IN) :: opts
+    REAL(C_DOUBLE), INTENT(OUT) :: out (*)
+    INTEGER(C_INT) :: h9g_get_dayquant
+  END FUNCTION
+  ! Device ms of the last h9g_get_dayquant's launches.
+  FUNCTION h9g_last_dayquant_ms (ctx) BIND(C, NAME='h9g_last_dayquant_ms')
+    IMPORT :: C_PTR, C_FLOAT
+    TYPE(C_PTR), VALUE :: ctx
+    REAL(C_FLOAT) :: h9g_last_dayquant_ms
+  END FUNCTION
+  ! The same kernel on hand-made records (n, 7, ntmax, nyears) of nt(y) days a
+  ! year, nseg slices a year (0: the product's): out (n, 1 + 2 nq, nres).
+  FUNCTION h9g_dayquant_selftest (device, n, nyears, nt, nseg, records, opts, out) &
+           BIND(C, NAME='h9g_dayquant_selftest')
+    IMPORT :: C_INT, C_INT32_T, C_FLOAT, C_DOUBLE, h9g_dayquant_opts
+    INTEGER(C_INT), VALUE :: device, n, nyears, nseg
+    INTEGER(C_INT32_T), INTENT(IN) :: nt (*)
+    REAL(C_FLOAT), INTENT(IN) :: records (*)
+    TYPE(h9g_dayquant_opts), INTENT(IN) :: opts
+    REAL(C_DOUBLE), INTENT(OUT) :: out (*)
+    INTEGER(C_INT) :: h9g_dayquant_selftest
+  END FUNCTION
+  ! One result of h9g_get_dayquant (ncell, 1 + 2 nq) to qxyYYYY.nc (or
+  ! qxyYYYY_YYYY.nc): count, lower, upper and the interpolated value per
+  ! quantile on axyYYYY.nc's grid, the series and years as global attributes.
+  FUNCTION h9g_write_qxy_nc (path, nx, ny, ncell, gid, year_first, year_last, opts, quant) &
+           BIND(C, NAME='h9g_write_qxy_nc')
+    IMPORT :: C_INT, C_CHAR, C_DOUBLE, C_INT64_T, h9g_dayquant_opts
+    CHARACTER(KIND=C_CHAR), INTENT(IN) :: path (*)
+    INTEGER(C_INT), VALUE :: nx, ny, ncell, year_first, year_last
+    INTEGER(C_INT64_T), INTENT(IN) :: gid (*)
+    TYPE(h9g_dayquant_opts), INTENT(IN) :: opts
+    REAL(C_DOUBLE), INTENT(IN) :: quant (*)
+    INTEGER(C_INT) :: h9g_write_qxy_nc
   END FUNCTION
   ! Spin-up to equilibrium: years jyear0 .. jyear0+nyears-1 (isolated cells,
   ! the forcing of year jyear0+k resident in slots(k+1)) repeated until the

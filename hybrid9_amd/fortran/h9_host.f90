@@ -70,6 +70,16 @@ PROGRAM H9_HOST
 ! dxyYYYY.nc is written, in both cell_order settings; it implies days and evap.
 ! The dxy file is then written only if days = 1 was set too.
 !
+! dayquant = 1 selects order statistics of one daily series on the device
+! (h9g_get_dayquant, DESIGN.md §7: the flow-duration curve, the median water
+! table, ...): quant_series (0: q, 1: e, 2..6: record rows 2..6; default 0) at
+! the probabilities quant_p (up to 16, each in [0, 1]; unset entries are -1;
+! default 0.05, 0.5, 0.95 -- hydrology's Q95 is p = 0.05), and writes each
+! year's to <out_dir>/qxyYYYY.nc (h9g_write_qxy_nc), in both cell_order
+! settings; it implies days and evap like daystats.  quant_pool = 1 pools the
+! years of every ordered call instead (cell_order = 1 only: an isolated run
+! retains one year) and writes <out_dir>/qxyYYYY_YYYY.nc per call.
+!
 ! spinup_cycles > 0 (0 = off, the default) spins the cold start of
 ! INIT.f90:707-811 up to equilibrium before the run proper (h9g_spinup,
 ! DESIGN.md §7): the run's first spinup_years years (default 1) are staged
@@ -107,6 +117,8 @@ REAL(C_FLOAT) :: zi (0:H9G_LMAX+1)
 CHARACTER (LEN = 512) :: input_mode, case_dir, out_dir, pgf_dir
 INTEGER :: nlayers, grow_on, device, grid, year0, nyears, nc_out, gnx, gny, gnland
 INTEGER :: cell_order, ordered_decades, daily, monthly, evap, days, daystats
+INTEGER :: dayquant, quant_series, quant_pool
+REAL(C_DOUBLE) :: quant_p (H9G_NQUANT_MAX)
 REAL(C_FLOAT) :: q_thr, theta_thr, zwt_thr, lai_thr
 INTEGER :: spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze
 REAL(C_DOUBLE) :: spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
@@ -115,6 +127,7 @@ NAMELIST /h9gpu/ input_mode, case_dir, out_dir, nlayers, grow_on, device, &
                  grid, year0, nyears, seed, pgf_dir, nc_out, gnx, gny, gnland, &
                  cell_order, ordered_decades, daily, monthly, evap, days, &
                  daystats, q_thr, theta_thr, zwt_thr, lai_thr, &
+                 dayquant, quant_series, quant_p, quant_pool, &
                  spinup_cycles, spinup_years, spinup_min_cycles, spinup_freeze, &
                  spinup_tol_water, spinup_tol_zwt, spinup_tol_plant
 CHARACTER (LEN = 600, KIND = C_CHAR), TARGET :: pgf_file (7)
@@ -122,7 +135,7 @@ TYPE(C_PTR) :: pgf_ptr (7)
 CHARACTER (LEN = *), PARAMETER :: pgf_var (7) = &
   (/ 'tas ', 'rlds', 'rsds', 'huss', 'ps  ', 'pr  ', 'rhs ' /)   ! READ_PGF.f90 order
 REAL(C_FLOAT) :: zc (H9G_LMAX)
-CHARACTER (LEN = 4) :: ydate
+CHARACTER (LEN = 4) :: ydate, ydate2
 
 ! --- case.nml of the harness (oracle/ref/h9ref_main.f90) -------------------
 INTEGER :: ncell, state_override, ntrace, trace_cells (64), lclim_mode
@@ -161,6 +174,9 @@ INTEGER :: mnx, mny
 TYPE(h9g_daystat_opts) :: dopts
 REAL(C_DOUBLE), ALLOCATABLE :: dstat (:,:)
 INTEGER :: rec_days
+! --- day quantiles (h9g_get_dayquant): one result's 1 + 2 nq rows -------------
+TYPE(h9g_dayquant_opts) :: qopts
+REAL(C_DOUBLE), ALLOCATABLE :: dquant (:,:)
 ! --- spin-up (h9g_spinup) ---------------------------------------------------
 TYPE(h9g_spinup_opts) :: sopts
 INTEGER(C_INT32_T) :: scycles
@@ -175,6 +191,7 @@ nlayers = 8; grow_on = 1; device = 0; grid = 1; year0 = 0; nyears = 0
 nc_out = 1; gnx = 0; gny = 0; gnland = 0; cell_order = 1; ordered_decades = 0
 monthly = 0; evap = 0; days = 0
 daystats = 0; q_thr = 1.0; theta_thr = 0.2; zwt_thr = 1000.0; lai_thr = 1.0
+dayquant = 0; quant_series = 0; quant_p = -1.0D0; quant_pool = 0
 spinup_cycles = 0; spinup_years = 1; spinup_min_cycles = 1; spinup_freeze = 1
 spinup_tol_water = HUGE (1.0D0); spinup_tol_zwt = HUGE (1.0D0); spinup_tol_plant = HUGE (1.0D0)
 daily = 0; INTERACTIVE = .FALSE.; lon_w = 0.0; lat_w = 0.0; lon_c_w = 1.0; lat_c_w = 1.0
@@ -409,7 +426,7 @@ IF (daily /= 0) THEN
   END IF
 END IF
 rec_days = 0
-IF (days /= 0 .OR. daystats /= 0) rec_days = 1
+IF (days /= 0 .OR. daystats /= 0 .OR. dayquant /= 0) rec_days = 1
 IF (rec_days /= 0) evap = 1
 IF (evap /= 0) CALL chk (h9g_set_evap (ctx, 1))
 IF (monthly /= 0) THEN
@@ -422,6 +439,22 @@ IF (daystats /= 0) THEN
   dopts%q_thr = q_thr; dopts%theta_thr = theta_thr; dopts%zwt_thr = zwt_thr; dopts%lai_thr = lai_thr
   dopts%reserved = 0
   ALLOCATE (dstat (ncell, H9G_NDAYSTAT))
+END IF
+IF (dayquant /= 0) THEN
+  IF (quant_pool /= 0 .AND. cell_order == 0) THEN
+    WRITE (*,*) 'h9_host: quant_pool = 1 needs cell_order = 1: an isolated run retains one year'
+    STOP 1
+  END IF
+  IF (ALL (quant_p < 0.0D0)) quant_p (1:3) = (/ 0.05D0, 0.5D0, 0.95D0 /)
+  qopts%series = quant_series; qopts%nq = 0; qopts%pooled = quant_pool; qopts%reserved = 0
+  qopts%p = 0.0D0
+  DO i = 1, H9G_NQUANT_MAX                   ! the entries that were set, in their order
+    IF (quant_p (i) >= 0.0D0) THEN
+      qopts%nq = qopts%nq + 1
+      qopts%p (qopts%nq) = quant_p (i)
+    END IF
+  END DO
+  ALLOCATE (dquant (ncell, 1 + 2 * qopts%nq))
 END IF
 IF (monthly /= 0 .OR. rec_days /= 0) THEN
   ALLOCATE (mgid (ncell))
@@ -478,7 +511,9 @@ IF (cell_order /= 0) THEN
       IF (monthly /= 0) CALL month_out (k - 1, dsyr + k - 1)
       IF (days /= 0) CALL days_out (k - 1, dsyr + k - 1)
       IF (daystats /= 0) CALL stats_out (k - 1, dsyr + k - 1)
+      IF (dayquant /= 0 .AND. quant_pool == 0) CALL quant_out (k - 1, 1, dsyr + k - 1)
     END DO
+    IF (dayquant /= 0 .AND. quant_pool /= 0 .AND. iyr == ndec) CALL quant_out (0, ndec, dsyr)
     CALL h9g_check_stop (ctx, rc)
     WRITE (*,'(A,I5,A,I5,A,12I3)') ' years', dsyr, ' -', deyr, ' in cell order: passes per decade', &
           passes (1:FLOOR (REAL (deyr - 1901) / 10.0) - FLOOR (REAL (dsyr - 1901) / 10.0) + 1)
@@ -498,6 +533,7 @@ DO iyr = 1, nyears
   IF (monthly /= 0) CALL month_out (0, jyear)
   IF (days /= 0) CALL days_out (0, jyear)
   IF (daystats /= 0) CALL stats_out (0, jyear)
+  IF (dayquant /= 0) CALL quant_out (0, 1, jyear)
   IF (daily /= 0) THEN                       ! flushed at the end of each reference decade
     CALL daily_year (0, jyear)
     IF (MODULO (jyear - 1900, 10) == 0 .OR. iyr == nyears) CALL daily_flush ()
@@ -572,6 +608,23 @@ CONTAINS
     CALL chk (h9g_write_sxy_nc (TRIM (out_dir)//'/sxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, ncell, mgid, y, &
                                 dopts, dstat))
   END SUBROUTINE stats_out
+
+  ! The day quantiles of years k .. k+nk-1 (0-based) of the last run, the
+  ! first of them calendar year y: one year to <out_dir>/qxyYYYY.nc, a pooled
+  ! span to <out_dir>/qxyYYYY_YYYY.nc.
+  SUBROUTINE quant_out (k, nk, y)
+    INTEGER, INTENT(IN) :: k, nk, y
+    CALL chk (h9g_get_dayquant (ctx, k, nk, qopts, dquant))
+    WRITE (ydate,'(I4)') y
+    WRITE (ydate2,'(I4)') y + nk - 1
+    IF (qopts%pooled /= 0) THEN
+      CALL chk (h9g_write_qxy_nc (TRIM (out_dir)//'/qxy'//ydate//'_'//ydate2//'.nc'//C_NULL_CHAR, mnx, mny, ncell, &
+                                  mgid, y, y + nk - 1, qopts, dquant))
+    ELSE
+      CALL chk (h9g_write_qxy_nc (TRIM (out_dir)//'/qxy'//ydate//'.nc'//C_NULL_CHAR, mnx, mny, ncell, mgid, y, y, &
+                                  qopts, dquant))
+    END IF
+  END SUBROUTINE quant_out
 
   ! The daily lines of year k (0-based) of the last run, calendar year y,
   ! appended to the current decade's.

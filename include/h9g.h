@@ -424,6 +424,58 @@ typedef struct {
 } h9g_daystat_opts;
 int h9g_get_daystats(h9g_ctx *ctx, int k0, int nk, const h9g_daystat_opts *opts, double *out);
 
+/* --- day quantiles: order statistics of a daily series from the day records */
+/* The day statistics are streaming reductions, one year at a time.  An order
+ * statistic of a cell's daily series -- the flow-duration curve, the median
+ * water table, a low percentile of top-layer moisture -- is not: it needs a
+ * selection, and it may pool several years.  h9g_get_dayquant selects on the
+ * device, from the day records where they lie, for years k0 .. k0+nk-1 of what
+ * the last h9g_run_year (k0 = 0, nk = 1), h9g_run_decade_ordered or
+ * h9g_run_ordered call recorded.  Synchronises, as h9g_get_days does.
+ * H9G_ESTATE if nothing was recorded; H9G_EINVAL for a bad span (a pooled span
+ * holds at most 512 years), a null pointer, `series` outside 0..6, `nq`
+ * outside 1..H9G_NQUANT_MAX, a `p` outside [0, 1] or NaN, `pooled` not 0 or 1,
+ * or a non-zero `reserved`.
+ *
+ * Candidates.  Series 0 and 1: q[d] and e[d] exactly as h9g_get_daystats
+ * defines them, one IEEE subtraction of the widened f32 running sums with
+ * S[-1] = 0 at every year's day 0 (in a pooled span every year restarts).
+ * Series 2..6: the f32 value of record row 2..6 widened to double.  A NaN
+ * candidate is skipped (a STOP day and later, a masked cell); m is the number
+ * of candidates left, per year, or over all years of the span when pooled.
+ * Order.  The total order on the doubles' bits: the sign-magnitude pattern
+ * mapped to a monotone unsigned key, so -0 sorts before +0 and equal values
+ * are interchangeable: x_(0) <= ... <= x_(m-1).
+ * Result.  out (nres, 1 + 2 nq, ncell) doubles, cell fastest, nres = pooled ?
+ * 1 : nk.  Row 0 is m.  For p[i], g = p[i] * (double)(m - 1) (one IEEE
+ * multiply) and j = floor(g): row 1 + 2i is x_(j), row 2 + 2i is
+ * x_(min(j + 1, m - 1)); with m = 0 both are NaN.  A cell that STOPs on day e
+ * contributes its days before e; a masked cell has m = 0.  Nothing is
+ * interpolated on the device and there is no floating-point sum anywhere:
+ * every row is exact and comparable bit for bit with a restatement in numpy
+ * (hybrid9_amd.day_order_stats).  The host derives the quantile, lo + (hi -
+ * lo) * (g - j) in double (lo itself where lo and hi are equal or g is whole,
+ * so an infinite value stays one): deterministic and derived, like the
+ * monthly means.  Hydrology counts from the top: its "Q95", the flow exceeded
+ * 95 % of the time, is p = 0.05 here, and "Q5" is p = 0.95.
+ * One kernel (h9g_dayquant_kernel) selects all nq ranks by the key's digits,
+ * most significant first, streaming the series once per digit and once more
+ * for the upper neighbours; it reads the records where h9g_get_days reads
+ * them and never copies them; no year kernel and no run path changes.  Its
+ * only allocation is the result, made by the first call, grown when needed
+ * and released with the context (not part of h9g_config_bytes); its working
+ * state lives in registers and LDS.  Without a call nothing is added
+ * anywhere: no launch, allocation or synchronisation. */
+#define H9G_NQUANT_MAX 16
+typedef struct {
+  int32_t series;      /* 0: q  1: e  2..6: record rows 2..6 (W, theta1, zwt, wa, LAI) */
+  int32_t nq;          /* 1 .. H9G_NQUANT_MAX */
+  int32_t pooled;      /* 0: one result per year of the span; 1: one for the whole span */
+  int32_t reserved;    /* 0 */
+  double p[H9G_NQUANT_MAX];   /* each in [0, 1], not NaN; any order, repeats allowed */
+} h9g_dayquant_opts;
+int h9g_get_dayquant(h9g_ctx *ctx, int k0, int nk, const h9g_dayquant_opts *opts, double *out);
+
 /* --- spin-up to equilibrium: cycle a forcing period, retire settled cells - */
 /* The model cold-starts from INIT.f90:707-811, and the reference's only
  * answer is to repeat years (its LCLIM loop re-reads the site years
@@ -573,6 +625,17 @@ int h9g_write_dxy_nc(const char *path, int nx, int ny, int nlayers,
  * four thresholds and the year are global attributes.  CDF-2.  Host only. */
 int h9g_write_sxy_nc(const char *path, int nx, int ny, int ncell, const int64_t *gid, int jyear,
                      const h9g_daystat_opts *opts, const double *stats);
+/* qxyYYYY.nc (qxyYYYY_YYYY.nc for a pooled span): one result of
+ * h9g_get_dayquant, quant (1 + 2 nq, ncell) doubles, of the cells gid on
+ * axyYYYY.nc's latitude / longitude grid: dimension `quantile` (nq) with the
+ * coordinate variable p, then count(latitude, longitude) (row 0) and lower,
+ * upper and value(quantile, latitude, longitude) -- the two order statistics
+ * and the quantile interpolated between them as described there -- all
+ * float64 with NaN _FillValue.  The series' name (q, e, soil_water, theta1,
+ * zwt, wa, LAI), year_first, year_last and pooled are global attributes.
+ * CDF-2.  Host only. */
+int h9g_write_qxy_nc(const char *path, int nx, int ny, int ncell, const int64_t *gid,
+                     int year_first, int year_last, const h9g_dayquant_opts *opts, const double *quant);
 /* READ_PGF.f90 / READ_NET_CDF_3DR.f90: days [t0, t0+nt) of variable 4
  * (time, lat, lon) of the 7 PGF files (tas rlds rsds huss ps pr rhs)
  * gathered at the grid ids gid into out (7, nt, ncell).  Host only. */
@@ -630,6 +693,8 @@ int h9g_launch_stats(h9g_ctx *ctx, double *out, int n, int reset);
 /* Device time (HIP events on the compute stream) of the launches of the last
  * h9g_get_daystats; 0 before the first. */
 float h9g_last_daystat_ms(h9g_ctx *ctx);
+/* The same of the last h9g_get_dayquant. */
+float h9g_last_dayquant_ms(h9g_ctx *ctx);
 /* Digest of the sources and compile flags of this library (16 hex digits;
  * hybrid9_amd/build.py build_id).  Profiles record it, and the bench
  * attaches counters only to the build they were measured on.  No GPU. */
@@ -666,6 +731,15 @@ int h9g_spin_selftest(int device, int n, int L, const float *state_prev, const f
  * show that the cut does not matter. */
 int h9g_daystat_selftest(int device, int n, int nt, int nseg, const float *records,
                          const h9g_daystat_opts *opts, double *out);
+/* h9g_get_dayquant on hand-made records, through the same kernel, with no
+ * context and no year run: nyears (1 .. 512) years of nt[y] (1 .. 65535) days,
+ * records (nyears, ntmax, 7, n) host with ntmax = max nt, out (nres, 1 + 2 nq,
+ * n).  nseg = 0 is the product's cut of a year into slices; nseg > 0 cuts
+ * every year into that many (1 .. 16: the largest workgroup built) through
+ * the same code, so a test can show that the cut does not matter.  Every
+ * argument is checked before a device is touched. */
+int h9g_dayquant_selftest(int device, int n, int nyears, const int32_t *nt, int nseg,
+                          const float *records, const h9g_dayquant_opts *opts, double *out);
 /* Hardware ids as the pair kernel's issue pacer decodes them: nblocks
  * workgroups of the pair kernel's shape and LDS size; per wave out[3w..3w+2]
  * = HW_REG_HW_ID, HW_REG_XCC_ID, 1 if every wave was resident at once. */
